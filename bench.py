@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the self-play hot path (BASELINE.json metric: MCTS node expansions/s + self-play episodes/s, 20x20 bin).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One STEP = one pass of the hot path over one batch of synthetic instances: a pool of `--pool` guillotine-split
@@ -9,21 +9,33 @@ One STEP = one pass of the hot path over one batch of synthetic instances: a poo
 through `--games` concurrent game slots per GPU (search kernels + FP32 CNN evaluator, inputs resident in HBM).  Every
 rank plays its own pool (weak scaling, no data-path collective); value = episodes all ranks finished / max-over-ranks time.
 
-Wall budget.  A c3 pool is 32 768 whole episodes (~30 s), so `--steps 20 --warmup 5` would be ~14 minutes.  The run
-therefore works against a wall budget (`--budget`, default 380 s from process start, covering the CPU baseline, start-up,
-graph capture, a short warm-up pass and the pools): it plays whole pools back to back until K + W are done or the next pool
-would not fit, then counts the LAST min(K, done) pools as the timed steps (earlier ones as warm-up) and reports the ACTUAL
-`steps`, `warmup` and `ms_per_step`.  The named configuration never shrinks.  The JSON line is printed after every
-completed pool (last line wins), so a run that is cut short still leaves a parsable line.
+A plain run sets up, plays a short warm-up pass and W warm-up pools, times exactly K pools (~24 s each at c3), writes the
+last pool's results if `--dump-outputs DIR` is given and prints ONE JSON line: episodes/s, expansions/s, `ms_per_step`.
+
+--dump-outputs DIR  after the timed pools, what the last one returned to its caller (BatchedSelfPlay.pop_finished: episode
+                    id, outcome, score, moves per episode, sorted by id) as DIR/<name>.npy in float64; with several ranks
+                    every rank writes its own, DIR/<name>_rank<r>.npy.  The instances are generated from fixed seeds and the
+                    evaluator from torch.manual_seed(0), so the same arguments give the same inputs on every run.
+                    The results are not bit-reproducible: k_pool_begin hands the pool's instances to the slots through an
+                    atomic counter, so which slot plays an episode varies between runs.  Two runs of one build with the same
+                    arguments (c3, one pool) agreed on every id, outcome and score and differed in the move count of about
+                    0.4 % of the episodes.
+
+--full adds everything beyond the headline figure:
+  cpu_baseline    the C oracle (oracle/rp_oracle.c) + the same CNN through PyTorch CPU, batch 1 per leaf as the
+                  reference does, on a bounded sample of the same workload, rank 0 at N = 1 only (before the GPU run)
+  roofline        the dominant kernel (FP32 MFMA bound) from HIP-event timings taken inside the timed region: every
+                  `--event-every`-th wave runs eagerly between events instead of as one graph launch
+  roofline_tree   the hand-written tree-walk kernels (k_search + k_commit, HBM bound): algorithmic bytes / event time
+  standalone      k_resstage16 alone on all slot rows, after the timed region
+  coach           with several ranks, one short CoachBPP iteration behind the pools (replay all-gather, gradient all-reduce)
+and a wall budget (`--budget`, default 380 s from process start): whole pools are played back to back until K + W are done
+or the next pool would not fit, the LAST min(K, done) pools count as the timed steps and the line reports the ACTUAL
+`steps`, `warmup` and `ms_per_step`.  Under a budget the JSON line is printed after every completed pool (last line wins),
+so a run that is cut short still leaves a parsable line.  A plain run has no budget unless `--budget` asks for one.
 
 `--gpus N` without WORLD_SIZE in the environment starts the N ranks itself (children are spawned before anything touches
 the GPU; the parent never does).
-
-The JSON line also carries
-  roofline        the dominant kernel (FP32 MFMA bound) from HIP-event timings taken inside the timed region
-  roofline_tree   the hand-written tree-walk kernels (k_search + k_commit, HBM bound): algorithmic bytes / event time
-  cpu_baseline    the C oracle (oracle/rp_oracle.c) + the same CNN through PyTorch CPU, batch 1 per leaf as the
-                  reference does, on a bounded sample of the same workload, rank 0 at N = 1 only
 """
 import argparse
 import hashlib
@@ -130,6 +142,29 @@ def make_instances(W, H, N, count, base_seed):
 
 def rank_buffer():
     return np.random.RandomState(12345).uniform(0.8, 1.0, 100)
+
+
+OUTPUT_NAMES = ("episode_id", "outcome", "score", "moves")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, finished, rank=0, world=1, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the pool's (episode ids, outcomes, scores, moves) as out_dir/<name>.npy in float64 (every value is exact:
+    ids, outcomes and moves are integers far below 2^53).  Past limit_bytes over all ranks, a fixed seeded sample of the episodes
+    is written, in id order.  With several ranks every rank writes its own files (<name>_rank<r>.npy).  Returns the paths."""
+    cols = [np.asarray(c).astype(np.float64) for c in finished]
+    n = len(cols[0])
+    max_rows = max(1, int(limit_bytes) // (8 * len(cols) * max(1, int(world))))
+    if n > max_rows:
+        keep = np.sort(np.random.RandomState(1234 + rank).choice(n, max_rows, replace=False))
+        cols = [c[keep] for c in cols]
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    paths = []
+    for name, col in zip(OUTPUT_NAMES, cols):
+        paths.append(os.path.join(out_dir, name + suffix + ".npy"))
+        np.save(paths[-1], col)
+    return paths
 
 
 class Args(dict):
@@ -297,86 +332,12 @@ def stage_kernel_flops(W, H):
 
 
 def build_output(cfg_name, W, H, N, sims, flops_leaf, games, pool, world, steps, warmup, requested, dt, tot, waves_rank0, groups, slots_group0,
-                 use_stem, compact_rows, per_wave, kernel_ms, solo, cpu_base, mean_score, mean_moves, extra, timed_rows=None):
+                 use_stem, compact_rows, per_wave, kernel_ms, solo, cpu_base, mean_score, mean_moves, extra, timed_rows=None, full=True):
     """tot: counters summed over ranks for the timed pools (+ 'waves'); per_wave: mean ms per wave of (search, stem/planes,
-    evaluator, commit) from the event-timed waves; kernel_ms: {kernel label: mean ms per launch} from HIP events."""
+    evaluator, commit) from the event-timed waves; kernel_ms: {kernel label: mean ms per launch} from HIP events.
+    full=False (a plain run): the headline figures and the counters only -- no roofline, per-kernel or CPU-baseline fields,
+    and per_wave / kernel_ms / solo / cpu_base are not read."""
     episodes = tot["episodes"]
-    K, A = key_bytes(W, H, N), W * N
-    # algorithmic bytes of the tree walk with THIS layout (DESIGN.md section 4).  Per selected node: 32 B header, 6 B best unvisited
-    # candidate, 22 B per visited entry (idx, N, Q, P), 6 B (child, action); 26 B per visited entry created (+ the rescan below);
-    # per backed-up edge 32 B (Q, N, Ns read + write); per expansion: key write + compare 2K, one 128 B probe bucket (16 slots),
-    # 32 B header write, 2 B action write per legal move (k_search) and, in k_commit, the 64 B header read-modify-write,
-    # the evaluator's 4A + 4 B output, 2 B action read + 4 B prior write per legal move.
-    # (round 3) the unvisited moves of a node are represented by ONE cached candidate (6 B: its pi and action); the prior run is scanned
-    # (4 B per legal move) only when that candidate is visited for the first time, i.e. once per new visited entry
-    mean_valid_sel = tot["sum_valid_select"] / max(tot["path_edges"], 1)
-    sel_bytes = 44.0 * tot["path_edges"] + 22.0 * tot["sum_visited_select"] + (26.0 + 4.0 * mean_valid_sel) * tot["visited_new"]
-    bak_bytes = 32.0 * tot["path_edges"]
-    exp_bytes = tot["expansions"] * (2 * K + 128 + 32 + 64 + 4 * A + 4) + 8.0 * tot["sum_valid_leaf"]
-    tree_bytes = sel_bytes + bak_bytes + exp_bytes
-    tree_ms = per_wave[0] + per_wave[3]
-    launches = max(tot["waves"], 1) * groups  # one k_search / evaluator / k_commit launch per group and wave
-    tree_bytes_per_wave = tree_bytes / launches
-    leaves_per_wave = tot["expansions"] / launches
-    stem_flops = 2 * 9 * (N + 1) * 16 * H * W if use_stem else 0  # first convolution: table sums in k_leaf_stem, not matrix-core work
-    # evaluator time per wave: with one slot group the waves run back to back, so it is the wall time per wave minus the three engine
-    # phases (single kernels, timed by events); the eagerly launched evaluator of the event-timed waves also carries the host's
-    # launch gaps between its kernels and is only the fallback for --groups > 1
-    eval_ms = per_wave[2]
-    if groups == 1 and waves_rank0 > 0:
-        eval_ms = dt * 1e3 / waves_rank0 - (per_wave[0] + per_wave[1] + per_wave[3])
-    rows = leaves_per_wave if compact_rows else slots_group0
-    nn_tflops = rows * (flops_leaf - stem_flops) / (eval_ms * 1e-3) / 1e12 if eval_ms > 0 else 0.0
-    kflops = stage_kernel_flops(W, H)
-    Hs, Ws = (H + 1) // 2, (W + 1) // 2
-    Hs2, Ws2 = (Hs + 1) // 2, (Ws + 1) // 2
-    Hs3, Ws3 = (Hs2 + 1) // 2, (Ws2 + 1) // 2
-    kbytes = {"k_resstage16 %dx%d" % (Hs, Ws): 2 * 4 * 16 * Hs * Ws,  # x in, result out, per leaf
-              "k_resstage32 %dx%d" % (Hs2, Ws2): 2 * 4 * 32 * Hs2 * Ws2, "k_resstage32 %dx%d" % (Hs3, Ws3): 2 * 4 * 32 * Hs3 * Ws3,
-              "k_convpool32 16->32 %dx%d" % (Hs, Ws): 4 * 16 * Hs * Ws + 4 * 32 * Hs2 * Ws2,
-              "k_convpool32 32->32 %dx%d" % (Hs2, Ws2): 4 * 32 * Hs2 * Ws2 + 4 * 32 * Hs3 * Ws3}
-    pmc, pmc_note = load_pmc_traffic()
-    roof = None
-    timed = {k: v for k, v in kernel_ms.items() if k in kflops}
-
-    # per-kernel figures: numerator and denominator from the SAME launches -- the leaves waiting in the event-timed waves themselves
-    # (read back with rp_leaf_count_async), not the mean over all waves
-    krows = timed_rows if (timed_rows and compact_rows) else rows
-
-    def kernel_roofline(kname):
-        rows = krows
-        kms, klaunches = timed[kname]
-        ach = rows * kflops[kname] / (kms * 1e-3) / 1e12
-        traffic = None
-        if pmc is not None:
-            # a kernel with several template instances in a wave (5x5 / 3x3 stages) appears once per instance in the PMC file
-            # ("k_resstage32<5>"): take the instance whose bytes per leaf are nearest this launch's algorithmic bytes
-            base = kname.split(" ")[0]
-            cands = [r for k, r in pmc.get("kernels", {}).items() if (k == base or k.startswith(base + "<")) and r.get("leaves_per_launch")]
-            if cands:  # the PMC passes cover the pool's first waves (every slot waiting): scale per leaf
-                rec = min(cands, key=lambda r: abs(r["hbm_bytes_per_launch"] / r["leaves_per_launch"] - kbytes.get(kname, 0)))
-                traffic = rec["hbm_bytes_per_launch"] / rec["leaves_per_launch"] * rows
-        return {"kernel": kname + " (FP32 MFMA, own HIP kernel)", "bound": "mfma", "achieved": ach, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                "frac": ach / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_note": pmc_note, "flops_per_launch": rows * kflops[kname],
-                "ms_per_launch": kms, "leaves_per_launch": rows, "launches_timed": klaunches,
-                "algorithmic_bytes_per_launch": rows * kbytes.get(kname, 0) or None}
-
-    roof_kernels = {k: kernel_roofline(k) for k in sorted(timed)}
-    if solo:  # k_resstage16 alone on ALL slot rows (random-free: the last stem output) after the timed region
-        for k, r in roof_kernels.items():
-            if k.startswith("k_resstage16 "):
-                r["standalone"] = solo
-                r["note"] = "achieved/frac: HIP events around the kernel's launches inside the timed region; standalone: the same kernel on all slot rows after the timed region"
-    if timed:
-        roof = roof_kernels[max(timed, key=lambda k: timed[k][0])]  # the dominant kernel by measured time
-    if roof is None:
-        roof = {"kernel": "CNN evaluator (all kernels of one forward over the slot batch)", "bound": "mfma", "achieved": nn_tflops,
-                "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": nn_tflops / PEAK_FP32_MFMA_TFLOPS, "traffic": None}
-    tree_traffic = None
-    if pmc is not None and all(k in pmc.get("kernels", {}) for k in ("k_search", "k_commit")):
-        ks = pmc["kernels"]
-        tree_traffic = sum(ks[k]["hbm_bytes_per_launch"] / ks[k]["leaves_per_launch"] for k in ("k_search", "k_commit")) * rows
-    tree_gbs = tree_bytes_per_wave / (tree_ms * 1e-3) / 1e9 if tree_ms > 0 else 0.0
     out = {
         "metric": "self-play episodes/sec (with MCTS node expansions/sec alongside)", "value": episodes / dt, "unit": "episodes/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / max(steps, 1) * 1e3, "higher_is_better": True,
@@ -392,22 +353,101 @@ def build_output(cfg_name, W, H, N, sims, flops_leaf, games, pool, world, steps,
                        "valid_per_leaf": tot["sum_valid_leaf"] / max(tot["expansions"], 1),
                        "expansions_per_sim": tot["expansions"] / max(tot["simulations"], 1),
                        "transposition_links": tot["transposition_links"], "nodes": tot["nodes"]},
-        "phase_ms_per_launch": {"search": per_wave[0], "leaf_stem" if use_stem else "leaf_planes": per_wave[1], "evaluator": per_wave[2], "commit": per_wave[3]},
-        "roofline": roof,
-        "roofline_kernels": roof_kernels,  # every own MFMA kernel of the evaluator, same fields
-        "roofline_evaluator": {"kernel": "whole CNN evaluator after the stem (fused MFMA kernels + heads) over the slot batch", "bound": "mfma",
-                               "achieved": nn_tflops, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": nn_tflops / PEAK_FP32_MFMA_TFLOPS,
-                               "traffic": None, "flops_per_leaf": flops_leaf - stem_flops, "flops_per_leaf_with_first_conv": flops_leaf,
-                               "leaves_per_launch": rows, "ms_per_launch": eval_ms},
-        "kernel_ms_per_launch": {k: v[0] for k, v in sorted(kernel_ms.items())},
-        "roofline_tree": {"kernel": "k_search + k_commit", "bound": "hbm", "achieved": tree_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                          "frac": tree_gbs / PEAK_HBM_GBS, "traffic": tree_traffic,
-                          "bytes_per_launch": tree_bytes_per_wave, "bytes_per_sim": tree_bytes / max(tot["simulations"], 1),
-                          "leaves_per_launch": leaves_per_wave, "slots_per_launch": slots_group0},
-        "cpu_baseline": cpu_base,
     }
+    if full:
+        K, A = key_bytes(W, H, N), W * N
+        # algorithmic bytes of the tree walk with THIS layout.  Per selected node: 32 B header, 6 B best unvisited
+        # candidate, 22 B per visited entry (idx, N, Q, P), 6 B (child, action); 26 B per visited entry created (+ the rescan below);
+        # per backed-up edge 32 B (Q, N, Ns read + write); per expansion: key write + compare 2K, one 128 B probe bucket (16 slots),
+        # 32 B header write, 2 B action write per legal move (k_search) and, in k_commit, the 64 B header read-modify-write,
+        # the evaluator's 4A + 4 B output, 2 B action read + 4 B prior write per legal move.
+        # (round 3) the unvisited moves of a node are represented by ONE cached candidate (6 B: its pi and action); the prior run is scanned
+        # (4 B per legal move) only when that candidate is visited for the first time, i.e. once per new visited entry
+        mean_valid_sel = tot["sum_valid_select"] / max(tot["path_edges"], 1)
+        sel_bytes = 44.0 * tot["path_edges"] + 22.0 * tot["sum_visited_select"] + (26.0 + 4.0 * mean_valid_sel) * tot["visited_new"]
+        bak_bytes = 32.0 * tot["path_edges"]
+        exp_bytes = tot["expansions"] * (2 * K + 128 + 32 + 64 + 4 * A + 4) + 8.0 * tot["sum_valid_leaf"]
+        tree_bytes = sel_bytes + bak_bytes + exp_bytes
+        tree_ms = per_wave[0] + per_wave[3]
+        launches = max(tot["waves"], 1) * groups  # one k_search / evaluator / k_commit launch per group and wave
+        tree_bytes_per_wave = tree_bytes / launches
+        leaves_per_wave = tot["expansions"] / launches
+        stem_flops = 2 * 9 * (N + 1) * 16 * H * W if use_stem else 0  # first convolution: table sums in k_leaf_stem, not matrix-core work
+        # evaluator time per wave: with one slot group the waves run back to back, so it is the wall time per wave minus the three engine
+        # phases (single kernels, timed by events); the eagerly launched evaluator of the event-timed waves also carries the host's
+        # launch gaps between its kernels and is only the fallback for --groups > 1
+        eval_ms = per_wave[2]
+        if groups == 1 and waves_rank0 > 0:
+            eval_ms = dt * 1e3 / waves_rank0 - (per_wave[0] + per_wave[1] + per_wave[3])
+        rows = leaves_per_wave if compact_rows else slots_group0
+        nn_tflops = rows * (flops_leaf - stem_flops) / (eval_ms * 1e-3) / 1e12 if eval_ms > 0 else 0.0
+        kflops = stage_kernel_flops(W, H)
+        Hs, Ws = (H + 1) // 2, (W + 1) // 2
+        Hs2, Ws2 = (Hs + 1) // 2, (Ws + 1) // 2
+        Hs3, Ws3 = (Hs2 + 1) // 2, (Ws2 + 1) // 2
+        kbytes = {"k_resstage16 %dx%d" % (Hs, Ws): 2 * 4 * 16 * Hs * Ws,  # x in, result out, per leaf
+                  "k_resstage32 %dx%d" % (Hs2, Ws2): 2 * 4 * 32 * Hs2 * Ws2, "k_resstage32 %dx%d" % (Hs3, Ws3): 2 * 4 * 32 * Hs3 * Ws3,
+                  "k_convpool32 16->32 %dx%d" % (Hs, Ws): 4 * 16 * Hs * Ws + 4 * 32 * Hs2 * Ws2,
+                  "k_convpool32 32->32 %dx%d" % (Hs2, Ws2): 4 * 32 * Hs2 * Ws2 + 4 * 32 * Hs3 * Ws3}
+        pmc, pmc_note = load_pmc_traffic()
+        roof = None
+        timed = {k: v for k, v in kernel_ms.items() if k in kflops}
+
+        # per-kernel figures: numerator and denominator from the SAME launches -- the leaves waiting in the event-timed waves themselves
+        # (read back with rp_leaf_count_async), not the mean over all waves
+        krows = timed_rows if (timed_rows and compact_rows) else rows
+
+        def kernel_roofline(kname):
+            rows = krows
+            kms, klaunches = timed[kname]
+            ach = rows * kflops[kname] / (kms * 1e-3) / 1e12
+            traffic = None
+            if pmc is not None:
+                # a kernel with several template instances in a wave (5x5 / 3x3 stages) appears once per instance in the PMC file
+                # ("k_resstage32<5>"): take the instance whose bytes per leaf are nearest this launch's algorithmic bytes
+                base = kname.split(" ")[0]
+                cands = [r for k, r in pmc.get("kernels", {}).items() if (k == base or k.startswith(base + "<")) and r.get("leaves_per_launch")]
+                if cands:  # the PMC passes cover the pool's first waves (every slot waiting): scale per leaf
+                    rec = min(cands, key=lambda r: abs(r["hbm_bytes_per_launch"] / r["leaves_per_launch"] - kbytes.get(kname, 0)))
+                    traffic = rec["hbm_bytes_per_launch"] / rec["leaves_per_launch"] * rows
+            return {"kernel": kname + " (FP32 MFMA, own HIP kernel)", "bound": "mfma", "achieved": ach, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                    "frac": ach / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_note": pmc_note, "flops_per_launch": rows * kflops[kname],
+                    "ms_per_launch": kms, "leaves_per_launch": rows, "launches_timed": klaunches,
+                    "algorithmic_bytes_per_launch": rows * kbytes.get(kname, 0) or None}
+
+        roof_kernels = {k: kernel_roofline(k) for k in sorted(timed)}
+        if solo:  # k_resstage16 alone on ALL slot rows (random-free: the last stem output) after the timed region
+            for k, r in roof_kernels.items():
+                if k.startswith("k_resstage16 "):
+                    r["standalone"] = solo
+                    r["note"] = "achieved/frac: HIP events around the kernel's launches inside the timed region; standalone: the same kernel on all slot rows after the timed region"
+        if timed:
+            roof = roof_kernels[max(timed, key=lambda k: timed[k][0])]  # the dominant kernel by measured time
+        if roof is None:
+            roof = {"kernel": "CNN evaluator (all kernels of one forward over the slot batch)", "bound": "mfma", "achieved": nn_tflops,
+                    "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": nn_tflops / PEAK_FP32_MFMA_TFLOPS, "traffic": None}
+        tree_traffic = None
+        if pmc is not None and all(k in pmc.get("kernels", {}) for k in ("k_search", "k_commit")):
+            ks = pmc["kernels"]
+            tree_traffic = sum(ks[k]["hbm_bytes_per_launch"] / ks[k]["leaves_per_launch"] for k in ("k_search", "k_commit")) * rows
+        tree_gbs = tree_bytes_per_wave / (tree_ms * 1e-3) / 1e9 if tree_ms > 0 else 0.0
+        out.update({
+            "phase_ms_per_launch": {"search": per_wave[0], "leaf_stem" if use_stem else "leaf_planes": per_wave[1], "evaluator": per_wave[2], "commit": per_wave[3]},
+            "roofline": roof,
+            "roofline_kernels": roof_kernels,  # every own MFMA kernel of the evaluator, same fields
+            "roofline_evaluator": {"kernel": "whole CNN evaluator after the stem (fused MFMA kernels + heads) over the slot batch", "bound": "mfma",
+                                   "achieved": nn_tflops, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": nn_tflops / PEAK_FP32_MFMA_TFLOPS,
+                                   "traffic": None, "flops_per_leaf": flops_leaf - stem_flops, "flops_per_leaf_with_first_conv": flops_leaf,
+                                   "leaves_per_launch": rows, "ms_per_launch": eval_ms},
+            "kernel_ms_per_launch": {k: v[0] for k, v in sorted(kernel_ms.items())},
+            "roofline_tree": {"kernel": "k_search + k_commit", "bound": "hbm", "achieved": tree_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                              "frac": tree_gbs / PEAK_HBM_GBS, "traffic": tree_traffic,
+                              "bytes_per_launch": tree_bytes_per_wave, "bytes_per_sim": tree_bytes / max(tot["simulations"], 1),
+                              "leaves_per_launch": leaves_per_wave, "slots_per_launch": slots_group0},
+            "cpu_baseline": cpu_base,
+        })
     out.update(extra)
-    if cpu_base:
+    if full and cpu_base:
         out["speedup_vs_cpu_baseline"] = out["value"] / cpu_base["value"]
     return out
 
@@ -495,8 +535,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--budget", type=float, default=float(os.environ.get("RP_BENCH_BUDGET_S", DEFAULT_BUDGET_S)),
-                    help="wall budget in seconds from process start; whole pools are played while the next one fits")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: CPU baseline, event-timed waves "
+                    "(phase / per-kernel / roofline figures), the standalone stage kernel, the multi-rank coach block; wall budget by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed pools, write the last pool's per-episode results "
+                    "(episode id, outcome, score, moves) to DIR/<name>.npy in float64")
+    ap.add_argument("--budget", type=float, default=float(os.environ["RP_BENCH_BUDGET_S"]) if os.environ.get("RP_BENCH_BUDGET_S") else None,
+                    help="wall budget in seconds from process start; whole pools are played while the next one fits "
+                    "(default: none, every requested pool is played; %.0f s with --full)" % DEFAULT_BUDGET_S)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="default c3 (c4 with --coach-iter)")
     ap.add_argument("--games", type=int, default=0, help="concurrent game slots per GPU (default: the configuration's, 32 768 for c3)")
     ap.add_argument("--pool", type=int, default=0, help="instances per step per GPU (default = games: every slot plays one episode)")
@@ -506,7 +551,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-reclaim", action="store_true", help="keep dead levels' arena chunks (needs ~5x the arena)")
     ap.add_argument("--groups", type=int, default=1, help="slot groups per GPU, each with its own stream and graph; 3 co-schedules the groups' kernels "
                     "(+4 %% episodes/s) but then no kernel has the GPU to itself and per-kernel durations stop meaning anything")
-    ap.add_argument("--step-cap", type=int, default=4, help="max simulations a slot runs per wave (bounds the launch tail; 3-6 measure the same, 16: -1.6 %)")
+    ap.add_argument("--step-cap", type=int, default=4, help="max simulations a slot runs per wave (bounds the launch tail; 3-6 measure the same, 16: -1.6 %%)")
     ap.add_argument("--no-stem", action="store_true", help="feed FP32 planes to the full CNN instead of computing conv1 + pool in the engine")
     ap.add_argument("--no-fuse", action="store_true", help="leave bias / ReLU / skip / pool to PyTorch's own element-wise kernels")
     ap.add_argument("--no-dense", action="store_true", help="keep <= 3x3-image convolutions on MIOpen instead of one GEMM each")
@@ -517,7 +562,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--warm-waves", type=int, default=96, help="waves of the short warm-up pass before the first pool")
-    ap.add_argument("--event-every", type=int, default=64, help="take per-phase / per-kernel HIP-event timings every n-th wave (those waves run eagerly between events instead of as one graph launch: 16 cost 0.4 %% of the episodes/s, 64 still time ~190 launches of every kernel per pool)")
+    ap.add_argument("--event-every", type=int, default=64, help="--full: take per-phase / per-kernel HIP-event timings every n-th wave (those waves run eagerly between events instead of as one graph launch: 16 cost 0.4 %% of the episodes/s, 64 still time ~190 launches of every kernel per pool)")
     ap.add_argument("--profile-waves", type=int, default=0, help="profiling aid: stop after this many waves per group and print no metric")
     ap.add_argument("--waves", type=int, default=0, help="bounded run for configurations whose pool takes many minutes (c5: ~100 k waves): play this many waves of "
                     "one pool and report expansions/s and simulations/s of that window (no episodes/s: no episode ends inside it)")
@@ -544,9 +589,13 @@ def main(argv=None):
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher: become one (this process never touches the GPU)
         sys.exit(spawn_ranks(a.gpus, argv))
 
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     t_start = float(os.environ.get("RP_BENCH_T0", T_PROCESS_START))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.no_coach_block and a.budget == DEFAULT_BUDGET_S:
-        a.budget = DEFAULT_BUDGET_S - 60.0  # room for the coach block behind the pools
+    if a.full and a.budget is None:  # a plain run plays every requested pool; --full keeps the whole command inside the driver's limit
+        a.budget = DEFAULT_BUDGET_S
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.no_coach_block:
+            a.budget = DEFAULT_BUDGET_S - 60.0  # room for the coach block behind the pools
     W, H, N, sims, flops_leaf, games_default, edge_factor_default = CONFIGS[a.config]
     a.edge_factor = a.edge_factor or edge_factor_default
     sims = a.sims or sims
@@ -554,7 +603,7 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_base = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.sims and not a.dry_run and not a.coach_iter:  # N = 1 only, before this process touches the GPU
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.sims and not a.dry_run and not a.coach_iter:  # N = 1 only, before this process touches the GPU
         cpu_base = run_cpu_baseline(a.config, a.cpu_budget)
     t_cpu_done = time.time()
 
@@ -628,6 +677,8 @@ def main(argv=None):
     cnt_used = [0]
 
     def play_pool(pool_idx, timed, max_waves=0):
+        """timed: take the HIP-event timings of every ev_every-th wave (--full).  Returns (waves, mean score, mean moves, the pool's
+        (episode ids, outcomes, scores, moves) sorted by id); a bounded window (max_waves) returns no results."""
         nonlocal phase_ms, phase_n
         # instances = ItemsGenerator.items_generator(seed), seeds 100 + index as in main_bpp.py:33, generated on the device
         # (bit-identical to the host generator; 32 768 instances through the Python generator would cost seconds of host time)
@@ -663,7 +714,7 @@ def main(argv=None):
                 for name, e0, e1 in kev:
                     kernel_ms.setdefault(name, []).append(e0.elapsed_time(e1))
                 del kev[:]
-                return waves, 0.0, 0.0
+                return waves, 0.0, 0.0, None
             if sp.active() == 0:
                 break
             if a.profile_waves and waves >= a.profile_waves:
@@ -677,9 +728,10 @@ def main(argv=None):
         for name, e0, e1 in kev:
             kernel_ms.setdefault(name, []).append(e0.elapsed_time(e1))
         del kev[:]
-        ids, _, score, moves = sp.pop_finished()
+        finished = sp.pop_finished()
+        ids, _, score, moves = finished
         assert len(ids) == pool, "pool not finished: %d of %d" % (len(ids), pool)
-        return waves, float(np.mean(score)), float(np.mean(moves))
+        return waves, float(np.mean(score)), float(np.mean(moves)), finished
 
     def barrier():
         if world > 1:
@@ -691,7 +743,7 @@ def main(argv=None):
         sp.counters(reset=True)
         barrier()
         t0 = time.time()
-        wv, _, _ = play_pool(0, True, max_waves=a.waves)
+        wv, _, _, _ = play_pool(0, True, max_waves=a.waves)
         barrier()
         dt = allreduce([time.time() - t0], dist.ReduceOp.MAX)[0]
         c = sp.counters()
@@ -712,21 +764,54 @@ def main(argv=None):
             dist.destroy_process_group()
         return
     # short warm-up pass: the first waves of a pool (every slot waits for the evaluator: the heaviest waves) through the captured
-    # graph and through the event-timed eager path, then the pool is abandoned (rp_begin_pool restarts every slot)
+    # graph (and with --full through the event-timed eager path), then the pool is abandoned (rp_begin_pool restarts every slot)
     if a.warm_waves > 0 and not a.profile_waves:
-        play_pool(0, True, max_waves=a.warm_waves)
+        play_pool(0, a.full, max_waves=a.warm_waves)
         sp.pop_finished()
         phase_ms[:] = 0; phase_n = 0; del kev[:]; kernel_ms.clear(); cnt_used[0] = 0
     sp.counters(reset=True)
     names = list(_lib.COUNTER_NAMES)
+    budget = a.budget if a.budget is not None else float("inf")
     barrier()
     bounds = [time.time()]       # pool boundaries on this rank's clock (after barrier + synchronize)
     snaps = [np.zeros(len(names) + 1)]  # cumulative counters (+ waves) of this rank at every boundary
     scores = []
     n_done, cum_waves = 0, 0
     solo = None
+    finished = None
+
+    def result_line(go):
+        """The JSON line for the pools played so far (every rank takes part in the reductions; rank 0 gets the line)."""
+        warm, timed = classify_pools(n_done, a.steps, a.warmup)
+        dt_local = bounds[-1] - bounds[warm]
+        delta = snaps[-1] - snaps[warm]
+        dt = allreduce([dt_local], dist.ReduceOp.MAX)[0]
+        tot_v = allreduce(delta.tolist(), dist.ReduceOp.SUM)
+        if rank != 0:
+            return None
+        tot = dict(zip(names + ["waves"], tot_v))
+        per_wave = phase_ms / max(phase_n, 1)
+        kms = {k: (float(np.mean(v)), len(v)) for k, v in kernel_ms.items()}
+        sc = scores[warm:]
+        longest = max(b1 - b0 for b0, b1 in zip(bounds[:-1], bounds[1:]))
+        cut = (not go) and n_done < a.steps + a.warmup
+        extra = {"ranks_joined": joined, "pools_played": n_done, "pools_planned": a.steps + a.warmup, "budget_cut": bool(cut),
+                 "steps_note": ("one step is a whole pool of %d episodes (%.1f s here): the requested %d + %d pools do not fit the %.0f s wall "
+                                "budget that keeps this command under the driver's limit, so %d pools were played and the last %d are timed"
+                                % (pool, longest, a.steps, a.warmup, budget, n_done, timed)) if cut else None,
+                 "pool_seconds": [b1 - b0 for b0, b1 in zip(bounds[:-1], bounds[1:])],
+                 "warmup_pass_waves": a.warm_waves, "wall_s_since_start": time.time() - t_start, "startup_s": bounds[0] - t_start,
+                 "device_bytes": sp.device_bytes, "arena_peak_per_slot": sp.arena_peak(), "final": not go}
+        if a.full:
+            extra["cpu_baseline_s"] = t_cpu_done - t_start
+        return build_output(a.config, W, H, N, sims, flops_leaf, games, pool, world, timed, warm, requested, dt, tot, float(delta[-1]),
+                            len(sp.groups), sp.groups[0].G, sp.use_stem, sp.compact_rows, per_wave, kms, solo, cpu_base,
+                            float(np.mean([s[0] for s in sc])), float(np.mean([s[1] for s in sc])), extra,
+                            timed_rows=float(cnt_host[:min(cnt_used[0], cnt_host.numel())].double().mean()) if cnt_used[0] else None,
+                            full=a.full)
+
     while True:
-        wv, mean_score, mean_moves = play_pool(n_done, True)
+        wv, mean_score, mean_moves, finished = play_pool(n_done, a.full)
         barrier()
         bounds.append(time.time())
         c = sp.counters()
@@ -735,56 +820,40 @@ def main(argv=None):
         scores.append((mean_score, mean_moves))
         n_done += 1
         longest = max(b1 - b0 for b0, b1 in zip(bounds[:-1], bounds[1:]))
-        go = should_continue(time.time() - t_start, n_done, longest, a.steps, a.warmup, a.budget)
+        go = should_continue(time.time() - t_start, n_done, longest, a.steps, a.warmup, budget)
         go = allreduce([1.0 if go else 0.0], dist.ReduceOp.MIN)[0] > 0.5 if world > 1 else go  # every rank must agree
-        if not go and n_done > 0 and solo is None and "stagefrag:0" in getattr(sp.nnet.nnet, "_dense", {}) and (W + 1) // 2 * ((H + 1) // 2) <= 128:
-            # the dominant stage kernel on ALL slot rows with the GPU to itself (after the timed region)
-            g0 = sp.groups[0]
-            dn = sp.nnet.nnet._dense
-            g0.eng.set_compact_rows(False)  # the row limit would read 0 after the last episode
-            with torch.cuda.stream(g0.stream):
-                o = torch.empty_like(g0.stem)
-                g0.eng.kernel_events = solo_ev = []
-                for _ in range(24):
-                    g0.eng.nn_resstage16(g0.stem, dn["stagefrag:0"], dn["stagebias:0"], o, None)
-                g0.eng.kernel_events = None
-            torch.cuda.synchronize(dev)
-            solo_ms = float(np.mean([e0.elapsed_time(e1) for _, e0, e1 in solo_ev[4:]]))
-            g0.eng.set_compact_rows(sp.compact_rows)
-            solo_fl = g0.G * stage_kernel_flops(W, H)["k_resstage16 %dx%d" % ((H + 1) // 2, (W + 1) // 2)]
-            solo = {"ms_per_launch": solo_ms, "leaves_per_launch": g0.G, "achieved": solo_fl / (solo_ms * 1e-3) / 1e12,
-                    "frac": solo_fl / (solo_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS}
-        # ---- the JSON line for the pools played so far (last line wins) ----
-        warm, timed = classify_pools(n_done, a.steps, a.warmup)
-        dt_local = bounds[-1] - bounds[warm]
-        delta = snaps[-1] - snaps[warm]
-        dt = allreduce([dt_local], dist.ReduceOp.MAX)[0]
-        tot_v = allreduce(delta.tolist(), dist.ReduceOp.SUM)
-        if rank == 0:
-            tot = dict(zip(names + ["waves"], tot_v))
-            per_wave = phase_ms / max(phase_n, 1)
-            kms = {k: (float(np.mean(v)), len(v)) for k, v in kernel_ms.items()}
-            sc = scores[warm:]
-            cut = (not go) and n_done < a.steps + a.warmup
-            extra = {"ranks_joined": joined, "pools_played": n_done, "pools_planned": a.steps + a.warmup, "budget_cut": bool(cut),
-                     "steps_note": ("one step is a whole pool of %d episodes (%.1f s here): the requested %d + %d pools do not fit the %.0f s wall "
-                                    "budget that keeps this command under the driver's limit, so %d pools were played and the last %d are timed"
-                                    % (pool, longest, a.steps, a.warmup, a.budget, n_done, timed)) if cut else None,
-                     "pool_seconds": [b1 - b0 for b0, b1 in zip(bounds[:-1], bounds[1:])],
-                     "warmup_pass_waves": a.warm_waves, "wall_s_since_start": time.time() - t_start, "startup_s": bounds[0] - t_start,
-                     "cpu_baseline_s": t_cpu_done - t_start, "device_bytes": sp.device_bytes, "arena_peak_per_slot": sp.arena_peak(),
-                     "final": not go}
-            out = build_output(a.config, W, H, N, sims, flops_leaf, games, pool, world, timed, warm, requested, dt, tot, float(delta[-1]),
-                               len(sp.groups), sp.groups[0].G, sp.use_stem, sp.compact_rows, per_wave, kms, solo, cpu_base,
-                               float(np.mean([s[0] for s in sc])), float(np.mean([s[1] for s in sc])), extra,
-                               timed_rows=float(cnt_host[:min(cnt_used[0], cnt_host.numel())].double().mean()) if cnt_used[0] else None)
-            print(json.dumps(out), flush=True)
         if not go:
             break
+        if a.budget is not None:  # a run that the budget cuts short still leaves a parsable line (last line wins)
+            out = result_line(go)
+            if out is not None:
+                print(json.dumps(out), flush=True)
+    if a.full and "stagefrag:0" in getattr(sp.nnet.nnet, "_dense", {}) and (W + 1) // 2 * ((H + 1) // 2) <= 128:
+        # the dominant stage kernel on ALL slot rows with the GPU to itself (after the timed region)
+        g0 = sp.groups[0]
+        dn = sp.nnet.nnet._dense
+        g0.eng.set_compact_rows(False)  # the row limit would read 0 after the last episode
+        with torch.cuda.stream(g0.stream):
+            o = torch.empty_like(g0.stem)
+            g0.eng.kernel_events = solo_ev = []
+            for _ in range(24):
+                g0.eng.nn_resstage16(g0.stem, dn["stagefrag:0"], dn["stagebias:0"], o, None)
+            g0.eng.kernel_events = None
+        torch.cuda.synchronize(dev)
+        solo_ms = float(np.mean([e0.elapsed_time(e1) for _, e0, e1 in solo_ev[4:]]))
+        g0.eng.set_compact_rows(sp.compact_rows)
+        solo_fl = g0.G * stage_kernel_flops(W, H)["k_resstage16 %dx%d" % ((H + 1) // 2, (W + 1) // 2)]
+        solo = {"ms_per_launch": solo_ms, "leaves_per_launch": g0.G, "achieved": solo_fl / (solo_ms * 1e-3) / 1e12,
+                "frac": solo_fl / (solo_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, finished, rank, world)
+    out = result_line(False)
+    if out is not None:
+        print(json.dumps(out), flush=True)
     # ---- several ranks: one short CoachBPP iteration for the configuration's two exchanges (BASELINE configs[3]) ----
     # Supplementary: the line above is final and already printed.  The block runs under a hard deadline -- a rank that fails or hangs in
     # a collective makes every rank leave with exit code 0 through its own watchdog, and the printed line stands.
-    if rdist.collectives_on() and not a.no_coach_block and not a.profile_waves:
+    if a.full and rdist.collectives_on() and not a.no_coach_block and not a.profile_waves:
         import threading
         threading.Timer(a.coach_block_s, lambda: os._exit(0)).start()
         try:

@@ -5,7 +5,7 @@ O=gpurun_out/$tag; mkdir -p $O
 for r in $(seq $reps); do
   for L in $libs; do
     n=$(basename $L .so | sed s/librp_engine_//)
-    RP_ENGINE_LIB=$PWD/$L python bench.py --steps 1 --warmup 0 --no-cpu-baseline "$@" > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || { tail -5 $O/bench_${n}_$r.err; exit 1; }
+    RP_ENGINE_LIB=$PWD/$L python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "$@" > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || { tail -5 $O/bench_${n}_$r.err; exit 1; }
     python - $O/bench_${n}_$r.json $n <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -4,7 +4,7 @@ tag=$1; reps=$2; var=$3; vals=$4
 O=gpurun_out/$tag; mkdir -p $O
 for r in $(seq $reps); do
   for v in $vals; do
-    env $var=$v python bench.py --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_${v}_$r.json 2> $O/bench_${v}_$r.err || { tail -5 $O/bench_${v}_$r.err; exit 1; }
+    env $var=$v python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_${v}_$r.json 2> $O/bench_${v}_$r.err || { tail -5 $O/bench_${v}_$r.err; exit 1; }
     python - $O/bench_${v}_$r.json "$var=$v" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

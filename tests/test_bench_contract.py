@@ -1,10 +1,12 @@
-"""bench.py's contract, checked on the CPU: the wall-budget planner keeps the driver's command inside its 600 s limit, the
-output builder emits every contract key, and `--gpus N` starts N ranks by itself (dry run: launch plumbing without GPU work)."""
+"""bench.py's contract, checked on the CPU: a plain run plays exactly the pools asked for, the wall-budget planner keeps a
+`--full` run inside its 600 s limit, the output builder emits every contract key (the plain line the headline only),
+`--dump-outputs` writes float arrays, and `--gpus N` starts N ranks by itself (dry run: launch plumbing without GPU work)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +15,7 @@ import bench  # noqa: E402
 
 
 def test_driver_command_fits_its_time_limit():
-    # python3 bench.py --gpus 1 --steps 20 --warmup 5: start-up between 40 s (warm box) and 200 s (cold first import of torch
+    # python3 bench.py --full --gpus 1 --steps 20 --warmup 5: start-up between 40 s (warm box) and 200 s (cold first import of torch
     # twice, CPU baseline, 139 GB of arenas, capture), c3 pools between 20 and 60 s
     for startup in (40, 90, 150, 200):
         for pool_s in (20, 30, 33.2, 40, 60):
@@ -39,6 +41,17 @@ def test_timed_steps_take_priority_over_warmup():
     assert bench.classify_pools(2, 1, 1) == (1, 1)
     assert not bench.should_continue(100.0, 25, 30.0, 20, 5, 380.0)
     assert bench.should_continue(1e9, 0, 0.0, 20, 5, 380.0)  # one pool is always played
+
+
+def test_plain_run_plays_exactly_the_requested_pools(monkeypatch):
+    monkeypatch.delenv("RP_BENCH_BUDGET_S", raising=False)
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.budget is None and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "2", "--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and a.budget is None  # main() gives --full its default budget
+    for steps, warmup in ((20, 5), (7, 0), (1, 1), (3, 2)):
+        n, warm, timed, _ = bench.simulate_plan(200, 60, steps, warmup, budget_s=float("inf"))
+        assert (n, warm, timed) == (steps + warmup, warmup, steps)
 
 
 def _fake_stats():
@@ -153,3 +166,44 @@ def test_eight_rank_dry_run_on_gloo():
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 8 and line["ranks_joined"] == 8 and line["backend"] == "gloo" and line["requested"]["gpus"] == 8
+
+
+def test_plain_line_carries_the_headline_only():
+    """Without --full the line has the headline figures and the counters; the roofline / per-kernel / CPU-baseline fields, which
+    need event-timed waves or runs of their own, are left out, and the figures it shares with the full line are the same."""
+    tot = _fake_stats()
+    args = ("c3", 20, 20, 32, 400, 10.01e6, 32768, 32768, 1, 2, 0, {"steps": 2, "warmup": 0}, 66.0, tot, 24000.0, 1, 32768, True, True)
+    out = bench.build_output(*args, None, None, None, None, 0.9, 30.0, {"ranks_joined": 1}, full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "expansions_per_s"):
+        assert k in out, k
+    for k in ("roofline", "roofline_kernels", "roofline_tree", "roofline_evaluator", "phase_ms_per_launch", "kernel_ms_per_launch", "cpu_baseline"):
+        assert k not in out, k
+    kms = {"k_resstage16 10x10": (0.55, 700)}
+    cpu = {"value": 2.8, "unit": "episodes/s", "cores": 32, "kind": "port", "sample": "x"}
+    full = bench.build_output(*args, [0.4, 0.25, 1.9, 0.12], kms, None, cpu, 0.9, 30.0, {"ranks_joined": 1})
+    for k in out:
+        assert out[k] == full[k], k
+    assert out["steps"] == 2 and abs(out["ms_per_step"] - 33000.0) < 1e-6 and out["higher_is_better"] is True
+    json.dumps(out)
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    ids = np.arange(1000, dtype=np.uint64)
+    oc = (np.arange(1000) % 3 - 1).astype(np.int32)
+    sc = np.linspace(0.5, 1.0, 1000)
+    mv = (np.arange(1000) % 32).astype(np.int32)
+    paths = bench.dump_outputs(str(tmp_path / "all"), (ids, oc, sc, mv))
+    assert [os.path.basename(p) for p in paths] == [n + ".npy" for n in bench.OUTPUT_NAMES]
+    got = [np.load(p) for p in paths]
+    assert all(g.dtype == np.float64 for g in got)
+    for g, ref in zip(got, (ids, oc, sc, mv)):
+        assert np.array_equal(g, ref.astype(np.float64))
+    # past the size limit: the same seeded sample of episodes every time, in id order, under the limit in all
+    a = [np.load(p) for p in bench.dump_outputs(str(tmp_path / "a"), (ids, oc, sc, mv), limit_bytes=8 * 4 * 100)]
+    b = [np.load(p) for p in bench.dump_outputs(str(tmp_path / "b"), (ids, oc, sc, mv), limit_bytes=8 * 4 * 100)]
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    assert len(a[0]) == 100 and np.all(np.diff(a[0]) > 0) and sum(x.nbytes for x in a) <= 8 * 4 * 100
+    assert np.array_equal(a[2], sc[a[0].astype(np.int64)])
+    # several ranks: one file set per rank
+    paths = bench.dump_outputs(str(tmp_path / "r"), (ids, oc, sc, mv), rank=1, world=2)
+    assert [os.path.basename(p) for p in paths] == [n + "_rank1.npy" for n in bench.OUTPUT_NAMES]

@@ -286,14 +286,14 @@ def test_mcts_class_matches_oracle_with_cnn_outputs_fed_back():
     mcts.close(); m.close()
 
 
-def test_coach_iteration_runs_and_trains():
+def test_coach_iteration_runs_and_trains(tmp_path):
     """One CoachBPP.learn iteration on the GPU: batched self-play, ranked-reward bookkeeping, replay tensors, training."""
     import torch
     from resource_packing_self_play_amd.CoachBPP import CoachBPP
     from resource_packing_self_play_amd.binpacking.BinPackingGame import ItemsGenerator
     d = np.load(os.path.join(GOLDEN, "nnet_c2_seed0.npz"))
     game, net, args = gpu_wrapper(d, numIters=2, numEps=12, iterStepThreshold=1, binH_min=4, binH=10, numScoresForRank=16,
-                                  numItersForTrainExamplesHistory=2, maxlenOfQueue=10000, numItems=8, checkpoint="/tmp/rp_coach_test/",
+                                  numItersForTrainExamplesHistory=2, maxlenOfQueue=10000, numItems=8, checkpoint=str(tmp_path),
                                   seed=3, use_graph=False)
     gen = ItemsGenerator(10, 10, 8)
     coach = CoachBPP(game, net, gen.items_generator(3), 100, gen, args)
@@ -306,7 +306,7 @@ def test_coach_iteration_runs_and_trains():
     assert torch.allclose(pi.sum(dim=1), torch.ones(len(pi), device=pi.device), atol=1e-5)
     assert (pi[-1] > 0).sum() == 1  # iteration 2 > iterStepThreshold: greedy one-hot targets (MCTS_bpp.py:43-49)
     assert any(not torch.equal(a, b.detach()) for a, b in zip(before, net.nnet.parameters()))
-    assert os.path.exists("/tmp/rp_coach_test/temp.pth.tar") and os.path.exists("/tmp/rp_coach_test/rewards_list_8_items.pkl")
+    assert os.path.exists(os.path.join(str(tmp_path), "temp.pth.tar")) and os.path.exists(os.path.join(str(tmp_path), "rewards_list_8_items.pkl"))
 
 
 @pytest.mark.parametrize("name", ["c2_seed0", "c3_seed0", "w15_trained"])
