@@ -50,7 +50,9 @@ typedef enum rp_status {
 typedef enum rp_move_rule {
     RP_MOVE_EXTERNAL = 0,   /* host supplies actions through rp_advance_roots */
     RP_MOVE_ARGMAX_FIRST = 1, /* lowest-index argmax of the root visit counts */
-    RP_MOVE_SAMPLE = 2      /* a ~ counts with a counter-based RNG keyed by (seed, episode id, move) */
+    RP_MOVE_SAMPLE = 2,     /* a ~ counts with a counter-based RNG keyed by (seed, episode id, move) */
+    RP_MOVE_ARGMAX_DRAW = 3 /* argmax of the root visit counts, ties drawn uniformly (MCTS_bpp.py:45-46): entry umulhi(x, m) of the
+                             * m most-visited actions in ascending order, x from the RP_MOVE_SAMPLE stream of (episode id, move) */
 } rp_move_rule;
 
 /* game phases reported by rp_game_status */
@@ -132,6 +134,11 @@ int rp_begin_pool(rp_ctx *ctx);
  * auto_restart pool directly on device (total area bin_w * bin_h as CoachBPP.py:119). */
 int rp_generate_items(rp_ctx *ctx, int64_t n, const uint32_t *seeds /*[n]*/, int32_t bin_w, int32_t bin_h, uint8_t *item_wh_out /*[n][N][2]*/);
 int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, const uint32_t *seeds, int32_t bin_w, int32_t bin_h, uint64_t first_id);
+/* Optional per-instance metadata of the pool set last by rp_set_instance_pool*: instance i plays as episode episode_id[i] (instead
+ * of first_id + i) and is ranked against the R2 threshold (bl[i], has_buf[i]) (instead of the rp_set_rank_buffer snapshot).  Any
+ * array may be NULL (that field keeps its default); n must equal the pool's size.  The next rp_set_instance_pool* clears it.  The
+ * metadata lives in device memory, so captured graphs stay valid. */
+int rp_set_instance_meta(rp_ctx *ctx, int64_t n, const uint64_t *episode_id /*[n]*/, const double *bl /*[n]*/, const uint8_t *has_buf /*[n]*/);
 /* R2 buffer snapshot (rewards_list argument of MCTS.getActionProb / getGameEnded, CoachBPP.py:76-91):
  * the threshold sorted[int(floor(len*alpha))-1] is recomputed and used by every slot from now on. */
 int rp_set_rank_buffer(rp_ctx *ctx, const double *rewards, int32_t n);

@@ -4,16 +4,18 @@
 
 `learn()` is the batched counterpart of the reference loop: the `numEps` episodes of an iteration are independent games
 (CoachBPP.py:123-134), so they run concurrently through `BatchedSelfPlay`, sharded over the ranks of a
-`torch.distributed` job.  Documented differences from the reference, all forced by concurrency or by its use of OS
-entropy:
-  * the ranked-reward buffer is a snapshot per iteration: every episode of an iteration is ranked against the buffer as
-    it stood when the iteration began; scores are appended in episode order afterwards (the reference appends after
-    each sequential episode, CoachBPP.py:134);
+`torch.distributed` job.  Documented differences from the reference (defaults; the first and the greedy tie have exact
+alternatives) and replacements of its use of OS entropy:
+  * args.rank_buffer = "snapshot" (default): every episode of an iteration is ranked against the buffer as it stood when the
+    iteration began; scores are appended in episode order afterwards (the reference appends after each sequential episode,
+    CoachBPP.py:134).  "sequential": the reference's running buffer, exactly -- the iteration is played against the snapshot,
+    then the episodes whose threshold class changed are replayed with their exact prefix threshold until none changes
+    (rank_buffer.py, DESIGN.md section 7);
   * moves are sampled with the engine's counter-based RNG instead of `np.random.seed(); np.random.choice`
     (CoachBPP.py:86-87): the draw of (episode, move) is a function of (sample seed, running episode number, move), the running
     number counts every episode this Coach has played (so iterations never reuse a stream) and the sample seed comes from OS
-    entropy like the reference's draws unless `args.sample_seed` pins it; greedy ties go to the lowest action instead of a
-    random one (MCTS_bpp.py:45-46);
+    entropy like the reference's draws unless `args.sample_seed` pins it; greedy ties go to the lowest action with
+    args.greedy_tie_break = "lowest" (default), or are drawn uniformly from that stream with "draw" (MCTS_bpp.py:45-46);
   * the replay set is kept PACKED (replay.PackedReplay: state key, item sizes, sparse visit counts -- ~0.4 KB per example
     instead of the reference's 110 KB of int64 planes + float list) and expanded to planes / pi per training minibatch;
   * the per-episode generator seeds are drawn up front from one OS-seeded stream (`drawIteration`);
@@ -75,6 +77,7 @@ class CoachBPP:
         self.metrics_log = []  # dicts with the reference's W&B metric names, one per iteration
         self.iteration_scores = []  # ep_scores of every iteration, in episode order
         self._selfplay = None
+        self.repair_log = []  # sequential rank buffer: per iteration rounds, episodes replayed per round, seconds, final (has_buf, bl)
 
     # ---- sequential episode, reference semantics (CoachBPP.py:50-99) --------------------------------------------------
     def executeEpisode(self, greedy=False):
@@ -159,7 +162,14 @@ class CoachBPP:
         mine = rdist.shard(n_eps)
         sp = self._driver(n_eps)
         greedy = i > args.iterStepThreshold  # :132
-        mode = (_lib.MOVE_ARGMAX_FIRST if greedy else _lib.MOVE_SAMPLE, bool(greedy)) if move_rule is None else (int(move_rule), bool(greedy))
+        tie = _opt(args, "greedy_tie_break", "lowest")
+        if tie not in ("lowest", "draw"):
+            raise ValueError("args.greedy_tie_break must be 'lowest' or 'draw', not %r" % (tie,))
+        argmax = _lib.MOVE_ARGMAX_DRAW if tie == "draw" else _lib.MOVE_ARGMAX_FIRST
+        mode = (argmax if greedy else _lib.MOVE_SAMPLE, bool(greedy)) if move_rule is None else (int(move_rule), bool(greedy))
+        rank_mode = _opt(args, "rank_buffer", "snapshot")
+        if rank_mode not in ("snapshot", "sequential"):
+            raise ValueError("args.rank_buffer must be 'snapshot' or 'sequential', not %r" % (rank_mode,))
         if getattr(self, "_move_mode", None) != mode:
             sp.set_move_rule(mode[0], onehot_examples=mode[1])  # re-captures the waves
             self._move_mode = mode
@@ -170,19 +180,30 @@ class CoachBPP:
         self.episodes_played += n_eps
         dev = self.nnet.device
         t0 = time.time()
+        from .binpacking.BinPackingGame import ItemsGenerator
+        host_items = bool(_opt(args, "host_items", False)) or not isinstance(self.gen, ItemsGenerator)
+
+        def play(idx, thresholds=None):
+            """Plays the iteration's episodes idx (global id base + index) -> (ids, scores, stats); thresholds: (bl, has_buf) per episode."""
+            seeds_p = np.asarray([seeds[k] for k in idx], dtype=np.uint32)
+            ids_p = None if thresholds is None else base + np.asarray(idx, dtype=np.int64)
+            first = base + int(idx[0])
+            if host_items:  # instances through gen.items_generator on the host (:127-130)
+                state = np.random.get_state()  # items_generator reseeds the global stream (BinPackingGame.py:258)
+                wh = np.array([[it[:2] for it in self.gen.items_generator(int(sd))] for sd in seeds_p], dtype=np.uint8)
+                np.random.set_state(state)
+                ids, _, score, _, st = sp.run(wh, np.full(len(idx), self.items_total_area, np.int32), self.rewards_list, first_id=first,
+                                              episode_ids=ids_p, thresholds=thresholds)
+            else:  # bit-identical instances generated on the device (k_items_generator), total area W * bin_height
+                ids, _, score, _, st = sp.run_from_seeds(seeds_p, self.rewards_list, first_id=first, bin_h=bin_height, bin_w=self.gen.bin_width,
+                                                         episode_ids=ids_p, thresholds=thresholds)
+            return ids.astype(np.int64), score, st
+
         if mine:
             first = base + mine[0]
-            seeds_mine = np.asarray([seeds[k] for k in mine], dtype=np.uint32)
-            from .binpacking.BinPackingGame import ItemsGenerator
-            if _opt(args, "host_items", False) or not isinstance(self.gen, ItemsGenerator):  # instances through gen.items_generator on the host (:127-130)
-                state = np.random.get_state()  # items_generator reseeds the global stream (BinPackingGame.py:258)
-                wh = np.array([[it[:2] for it in self.gen.items_generator(int(sd))] for sd in seeds_mine], dtype=np.uint8)
-                np.random.set_state(state)
-                ids, outcome, score, moves, stats = sp.run(wh, np.full(len(mine), self.items_total_area, np.int32), self.rewards_list, first_id=first)
-            else:  # bit-identical instances generated on the device (k_items_generator), total area W * bin_height
-                ids, outcome, score, moves, stats = sp.run_from_seeds(seeds_mine, self.rewards_list, first_id=first, bin_h=bin_height, bin_w=self.gen.bin_width)
+            ids, score, stats = play(mine)
             local = torch.zeros(len(mine), dtype=torch.float64, device=dev)
-            local[torch.as_tensor(ids.astype(np.int64) - first, device=dev)] = torch.as_tensor(score, device=dev)
+            local[torch.as_tensor(ids - first, device=dev)] = torch.as_tensor(score, device=dev)
             replay = sp.examples_packed()
         else:  # more ranks than episodes: nothing to play, but every collective below is still joined
             from .replay import PackedReplay
@@ -192,21 +213,78 @@ class CoachBPP:
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         t_play = time.time() - t0
+        ep_scores = self._gather_scores(mine, local, n_eps)
+        repair = None
+        if rank_mode == "sequential":
+            ep_scores, replay, repair = self._repair_sequential(ep_scores, replay, play, base, bin_height, seeds, host_items)
         self.last_example_keys = replay.episode * (self.game.num_items + 1) + replay.move.to(torch.int64) - base * (self.game.num_items + 1)  # LOCAL examples (tests)
         if rdist.collectives_on():
-            mine_t = torch.as_tensor(mine, dtype=torch.int64, device=dev)
-            gathered = rdist.all_gather_variable(torch.stack([mine_t.to(torch.float64), local], dim=1))
-            ep_scores = np.zeros(n_eps)
-            g = gathered.cpu().numpy()
-            ep_scores[g[:, 0].astype(np.int64)] = g[:, 1]
             replay = rdist.all_gather_packed(replay)  # rank order -> (episode, move) order, the same on every rank
             exch = dict(rdist.last_exchange)
         else:
-            ep_scores = local.cpu().numpy()
             exch = dict(bytes_sent=0, bytes_received=0, ms=0.0, examples=len(replay))
         self.last_stats = stats
         self.timings.append(dict(iteration=i, episodes=n_eps, selfplay_s=t_play, examples=len(replay), replay_bytes=replay.nbytes, exchange=exch))
+        if repair is not None:
+            self.timings[-1].update(rank_buffer="sequential", repair_rounds=repair["rounds"], replayed=list(repair["replayed"]), replay_s=repair["replay_s"])
         return [float(s) for s in ep_scores], replay
+
+    def _gather_scores(self, idx, local, n_eps):
+        """Scores [n_eps] float64 of the iteration on every rank from each rank's (indices idx, scores local); unplayed entries 0."""
+        import torch
+        ep_scores = np.zeros(n_eps)
+        if rdist.collectives_on():
+            idx_t = torch.as_tensor(np.asarray(idx, dtype=np.int64), dtype=torch.int64, device=local.device)
+            g = rdist.all_gather_variable(torch.stack([idx_t.to(torch.float64), local], dim=1)).cpu().numpy()
+            ep_scores[g[:, 0].astype(np.int64)] = g[:, 1]
+        else:
+            ep_scores[np.asarray(idx, dtype=np.int64)] = local.cpu().numpy()
+        return ep_scores
+
+    def _repair_sequential(self, ep_scores, replay, play, base, bin_height, seeds, host_items):
+        """args.rank_buffer = "sequential": replays, round by round, the episodes whose threshold class differs from that of their
+        exact prefix threshold (rank_buffer.repair).  Every rank computes the same plan from the same float64 scores and plays its
+        block of it (a rank with nothing to play still joins the round's all-gather); the replayed episodes' examples replace the
+        stale ones on whichever rank held them.  -> (final scores, local PackedReplay, repair record)."""
+        import time
+        import torch
+        from . import rank_buffer as rb
+        from .replay import PackedReplay
+        args, sp, dev = self.args, self._driver(len(seeds)), self.nnet.device
+        W, H = self.game.bin_width, self.game.bin_height
+        if host_items:
+            R = rb.superset_scores(H)  # the instances' item heights stay on the host side of gen.items_generator
+        else:  # b = max(ceil(area / W), max_h) of every instance: area W_gen * bin_height (:119), max_h from the device generator
+            wh = sp.eng.generate_items(np.asarray(seeds, dtype=np.uint32), bin_w=self.gen.bin_width, bin_h=bin_height)
+            R = rb.reachable_scores(np.full(len(seeds), self.items_total_area), wh[:, :, 1].max(axis=1), W, H)
+        state = dict(replay=replay, seconds=0.0)
+
+        def play_round(idx, bl, has):
+            t0 = time.time()
+            pos = {int(k): j for j, k in enumerate(idx)}
+            mine = rb.shard_plan(idx, rdist.rank(), rdist.world_size())
+            rep = state["replay"]
+            gone = torch.as_tensor(np.asarray(idx, dtype=np.int64) + base, device=dev)
+            keep = torch.nonzero(~torch.isin(rep.episode, gone)).flatten()
+            parts = [rep.select(keep)]
+            local = torch.zeros(len(mine), dtype=torch.float64, device=dev)
+            if len(mine):
+                sel = np.asarray([pos[int(k)] for k in mine])
+                sp.clear_examples()
+                ids, score, _ = play(mine, (np.asarray(bl)[sel], np.asarray(has)[sel]))
+                order = np.searchsorted(np.asarray(mine, dtype=np.int64) + base, ids)
+                local[torch.as_tensor(order, device=dev)] = torch.as_tensor(score, device=dev)
+                parts.append(sp.examples_packed())
+            state["replay"] = PackedReplay.cat(parts).sort_by_episode_move().compact() if len(parts) > 1 else parts[0]
+            got = self._gather_scores(mine, local, len(seeds))
+            state["seconds"] += time.time() - t0
+            return got[np.asarray(idx, dtype=np.int64)]
+
+        res = rb.repair(self.rewards_list, ep_scores, float(args.alpha), R, play_round)
+        record = dict(rounds=res["rounds"], replayed=res["replayed"], replay_s=state["seconds"], bl=res["bl"], has_buf=res["has_buf"],
+                      keys_played=res["keys_played"], R=R)
+        self.repair_log.append(record)
+        return res["scores"], state["replay"], record
 
     def learn(self):
         import time

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
 ABI_VERSION = 4
 
-MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE = 0, 1, 2
+MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
 KIND_WEAK, KIND_F32, KIND_F64 = 0, 1, 2
 ERR_ARG, ERR_DEVICE, ERR_CAPACITY, ERR_ASSERT, ERR_STATE = -1, -2, -3, -4, -5
@@ -53,6 +53,7 @@ _SIGS = {
     "rp_begin_pool": (C.c_int, [_vp]),
     "rp_generate_items": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "rp_set_instance_pool_seeds": (C.c_int, [_vp, _i64, _vp, _i32, _i32, C.c_uint64]),
+    "rp_set_instance_meta": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "rp_set_rank_buffer": (C.c_int, [_vp, _vp, _i32]),
     "rp_set_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_set_stream": (C.c_int, [_vp, _vp]),
@@ -169,6 +170,7 @@ class Engine:
         if rc != 0:
             raise EngineError(rc, self.L.rp_last_error(None).decode())
         self.h = h
+        self.pool_size = 0  # size of the pool set last (rp_set_instance_pool*)
 
     def close(self):
         if getattr(self, "h", None):
@@ -238,6 +240,21 @@ class Engine:
     def set_instance_pool_seeds(self, seeds, bin_w=None, bin_h=None, first_id=0):
         seeds = _arr(seeds, np.uint32).reshape(-1)
         self._ck(self.L.rp_set_instance_pool_seeds(self.h, seeds.shape[0], _ptr(seeds), int(bin_w or self.W), int(bin_h or self.H), int(first_id)))
+        self.pool_size = int(seeds.shape[0])
+
+    def set_instance_pool(self, item_wh, total_area, first_id=0):
+        item_wh = _arr(item_wh, np.uint8); n = item_wh.shape[0]
+        item_wh = _arr(item_wh, np.uint8, (n, self.N, 2)); total_area = _arr(total_area, np.int32, (n,))
+        self._ck(self.L.rp_set_instance_pool(self.h, n, _ptr(item_wh), _ptr(total_area), int(first_id)))
+        self.pool_size = int(n)
+
+    def set_instance_meta(self, episode_id=None, bl=None, has_buf=None):
+        """Per-instance episode ids and R2 thresholds of the pool set last (rp_set_instance_meta); None keeps a field's default."""
+        n = self.pool_size
+        ids = None if episode_id is None else _arr(episode_id, np.uint64, (n,))
+        bl = None if bl is None else _arr(bl, np.float64, (n,))
+        has = None if has_buf is None else _arr(np.asarray(has_buf) != 0, np.uint8, (n,))
+        self._ck(self.L.rp_set_instance_meta(self.h, n, _ptr(ids), _ptr(bl), _ptr(has)))
 
     def set_roots(self, rows, remaining, first=0):
         rows = _arr(rows, np.uint64); count = rows.shape[0]

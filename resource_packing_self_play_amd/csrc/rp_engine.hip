@@ -76,6 +76,11 @@ struct PoolDesc {
     unsigned long long first_id;
     const unsigned char *wh;  // [n_instances][N][2]
     const int *area, *max_h;
+    // optional per-instance metadata (rp_set_instance_meta), NULL = the default: episode id first_id + index, the rp_set_rank_buffer
+    // snapshot's R2 threshold.  Read only when a slot restarts (k_pool_begin, k_moves), never by k_search.
+    const unsigned long long *episode_id;
+    const double *bl;
+    const unsigned char *has_buf;
 };
 // A visited edge: one 32-byte record = two 16-byte loads.  (Five parallel arrays -- idx, N, child, Q, P -- cost a node with a few visited
 // edges five cache lines per selection and a backup two; the record costs one.)
@@ -944,8 +949,9 @@ template <typename row_t, bool BIG = true> struct Tree {
 __device__ u64 sample_u64(u64 seed, u64 episode, u64 move) { return mix64(mix64(mix64(seed) ^ episode) ^ move); }
 
 // CoachBPP.executeEpisode's move (CoachBPP.py:86-99) for one slot whose search budget is spent.
-// action < 0: pick by p.move_rule.  Leaves phase RUNNING, EPISODE_DONE or FAILED.
-template <typename row_t, bool BIG>
+// action < 0: pick by p.move_rule.  Leaves phase RUNNING, EPISODE_DONE or FAILED.  DRAW = false (k_advance, which always passes an
+// action) leaves the RP_MOVE_ARGMAX_DRAW branch out of the kernel.
+template <typename row_t, bool BIG, bool DRAW = true>
 __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root, int action) {
     root = uni(root);
     NodeHdr hd = t.load_hdr(root);
@@ -977,6 +983,31 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
             if (on > best_n || (on == best_n && ok < best_k)) { best_n = on; best_k = ok; best_e = oe; }
         }
         chosen = best_n ? best_e : NONE32;
+    } else if (DRAW && p.move_rule == RP_MOVE_ARGMAX_DRAW) {  // bestA = np.random.choice(bestAs) (MCTS_bpp.py:45-46) on the RP_MOVE_SAMPLE stream
+        u32 best_n = 0, m = 0;
+        for (u32 j = lane; j < hd.vis_n; j += 64) best_n = max(best_n, t.vis[hd.vis_off + j].n & NSA_MASK);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) best_n = max(best_n, (u32)__shfl_xor(best_n, o));
+        for (u32 j = lane; j < hd.vis_n; j += 64) m += (t.vis[hd.vis_off + j].n & NSA_MASK) == best_n ? 1u : 0u;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) m += (u32)__shfl_xor(m, o);
+        if (best_n) {  // entry `pick` of the m maxima in ascending action order (bestAs is np.argwhere's ascending list)
+            const u32 pick = (u32)__umul64hi(sample_u64(p.seed, p.episode[g], (u64)p.moves[g]), (u64)m);
+            for (u32 jb = 0; jb < hd.vis_n && chosen == NONE32; jb += 64) {
+                u32 j = jb + lane;
+                bool act = j < hd.vis_n;
+                u32 e = hd.vis_off + (act ? j : 0);
+                u32 k = t.vis[e].idx;
+                bool top = act && (t.vis[e].n & NSA_MASK) == best_n;
+                u32 below = 0;
+                for (u32 i = 0; i < hd.vis_n; ++i) {  // maxima of lower actions (uniform loads)
+                    u32 e2 = hd.vis_off + i;
+                    if ((t.vis[e2].n & NSA_MASK) == best_n && t.vis[e2].idx < k) below++;
+                }
+                u64 b = __ballot(top && below == pick);
+                if (b) chosen = hd.vis_off + jb + (__ffsll((long long)b) - 1);
+            }
+        }
     } else {  // RP_MOVE_SAMPLE: a ~ counts; inverse CDF in ascending action order over the (unordered) visited block
         u64 total = 0;
         for (u32 j = lane; j < hd.vis_n; j += 64) total += t.vis[hd.vis_off + j].n & NSA_MASK;
@@ -1098,8 +1129,8 @@ __device__ void restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &
     for (int s = lane; s < p.table_cap; s += 64) t.table[s] = 0ull;
     if (lane == 0) {
         p.total_area[g] = pd.area[idx]; p.max_h[g] = pd.max_h[idx];
-        p.episode[g] = pd.first_id + idx; p.moves[g] = 0; p.sims_done[g] = 0;
-        p.bl[g] = *p.g_bl; p.has_buf[g] = *p.g_has_buf;
+        p.episode[g] = pd.episode_id ? pd.episode_id[idx] : pd.first_id + idx; p.moves[g] = 0; p.sims_done[g] = 0;
+        p.bl[g] = pd.bl ? pd.bl[idx] : *p.g_bl; p.has_buf[g] = pd.has_buf ? (int)pd.has_buf[idx] : *p.g_has_buf;
         p.last_outcome[g] = 0; p.last_score[g] = 0.0;
     }
     t.n_nodes = 0;
@@ -1820,7 +1851,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_advance(DP p, int firs
     __shared__ u32 s_vmask[WAVES_PER_BLOCK][MAX_MASK_WORDS];
     Tree<row_t> t(p, g, s_stage + (size_t)wave_in_block() * p.A, s_vm[wave_in_block()], s_vmask[wave_in_block()]);
     u32 root = p.root[g];
-    play_move_impl<row_t>(p, t, g, root, action[k]);
+    play_move_impl<row_t, true, false>(p, t, g, root, action[k]);
     t.store_sizes();
     t.flush_counters();
 }
@@ -3317,6 +3348,10 @@ struct rp_ctx {
     u8 *pool_wh;
     int *pool_area, *pool_max_h;
     int64_t pool_cap;
+    u64 *meta_id;       // rp_set_instance_meta's arrays (capacity meta_cap)
+    double *meta_bl;
+    u8 *meta_has;
+    int64_t meta_cap;
     int n_cu = 256;                   // compute units and LDS bytes per CU of the device (hipDeviceProp, read once in rp_create)
     size_t lds_per_cu = 160 * 1024;
     int compact_rows = 0;             // rp_set_compact_rows: rp_search_step(ctx, NULL) lists the waiting slots on the device too
@@ -3457,6 +3492,7 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     ctx->bytes = 0;
     ctx->fin_popped = 0;
     ctx->pool_wh = nullptr; ctx->pool_area = nullptr; ctx->pool_max_h = nullptr; ctx->pool_cap = 0;
+    ctx->meta_id = nullptr; ctx->meta_bl = nullptr; ctx->meta_has = nullptr; ctx->meta_cap = 0;
     ctx->stream = (hipStream_t)cfg->stream;
     hipError_t e = hipSetDevice(cfg->device);
     if (e != hipSuccess) { delete ctx; return fail(nullptr, RP_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(e)); }
@@ -3767,7 +3803,7 @@ extern "C" int rp_set_compact_rows(rp_ctx *ctx, int32_t enable) {
 }
 
 extern "C" int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples) {
-    if (!ctx || move_rule < RP_MOVE_EXTERNAL || move_rule > RP_MOVE_SAMPLE) return fail(ctx, RP_ERR_ARG, "rp_set_move_rule: bad argument");
+    if (!ctx || move_rule < RP_MOVE_EXTERNAL || move_rule > RP_MOVE_ARGMAX_DRAW) return fail(ctx, RP_ERR_ARG, "rp_set_move_rule: bad argument");
     ctx->d.move_rule = move_rule;
     ctx->d.onehot_examples = onehot_examples ? 1 : 0;
     ctx->cfg.move_rule = move_rule;
@@ -4364,6 +4400,26 @@ extern "C" int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, cons
     d.pool_wh = ctx->pool_wh; d.pool_area = ctx->pool_area; d.pool_max_h = ctx->pool_max_h;
     d.n_instances = n_instances; d.first_id = first_id;
     const PoolDesc pd = {(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};
+    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &pd, sizeof pd, hipMemcpyHostToDevice));
+    return RP_OK;
+}
+
+extern "C" int rp_set_instance_meta(rp_ctx *ctx, int64_t n, const uint64_t *episode_id, const double *bl, const uint8_t *has_buf) {
+    if (!ctx || !ctx->d.pool_wh || n != ctx->d.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_meta: n must equal the size of the pool set last");
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // slots of the previous pool may still read the arrays
+    if (n > ctx->meta_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
+        ALLOC(ctx, ctx->meta_id, (size_t)n);
+        ALLOC(ctx, ctx->meta_bl, (size_t)n);
+        ALLOC(ctx, ctx->meta_has, (size_t)n);
+        ctx->meta_cap = n;
+    }
+    if (n > 0 && episode_id) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_id, episode_id, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0 && bl) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_bl, bl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0 && has_buf) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_has, has_buf, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const DP &d = ctx->d;
+    const PoolDesc pd = {(long long)d.n_instances, (unsigned long long)d.first_id, d.pool_wh, d.pool_area, d.pool_max_h,
+                         episode_id ? ctx->meta_id : nullptr, bl ? ctx->meta_bl : nullptr, has_buf ? ctx->meta_has : nullptr};
     HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &pd, sizeof pd, hipMemcpyHostToDevice));
     return RP_OK;
 }

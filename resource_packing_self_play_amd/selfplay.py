@@ -11,7 +11,7 @@ own engine context, HIP stream and captured HIP graph of one simulation WAVE:
     rp_commit_eval      mask / renormalise / expand / backup on device
 
 The groups' waves are launched alternately on their streams, so the latency-bound tree walk of one group runs while the
-CNN of the other occupies the matrix cores.  Moves are played on device (`RP_MOVE_SAMPLE` / `RP_MOVE_ARGMAX_FIRST`) and a
+CNN of the other occupies the matrix cores.  Moves are played on device (`RP_MOVE_SAMPLE` / `RP_MOVE_ARGMAX_FIRST` / `_DRAW`) and a
 finished slot immediately pulls the next instance of its group's pool, so the evaluator batch stays full until the pool
 runs dry.
 """
@@ -211,13 +211,33 @@ class BatchedSelfPlay:
             out.append((lo, hi)); lo = hi
         return out
 
-    def start(self, item_wh, total_area, rewards_list=(), first_id=0):
-        """The pool is cut into one contiguous block per group; instance i's episode id is first_id + i."""
+    def _set_meta(self, g, lo, hi, episode_ids, thresholds):
+        """Per-instance episode ids / R2 thresholds (bl [n], has_buf [n]) of group g's block lo:hi (rp_set_instance_meta)."""
+        if episode_ids is None and thresholds is None:
+            return
+        ids = None if episode_ids is None else np.asarray(episode_ids, dtype=np.uint64)[lo:hi]
+        bl = has = None
+        if thresholds is not None:
+            bl = np.asarray(thresholds[0], dtype=np.float64)[lo:hi]
+            has = np.asarray(thresholds[1])[lo:hi]
+        g.eng.set_instance_meta(ids, bl, has)
+
+    @staticmethod
+    def _check_meta(n, episode_ids, thresholds):
+        if episode_ids is not None and len(episode_ids) != n:
+            raise ValueError("episode_ids needs one id per instance")
+        if thresholds is not None and (len(thresholds) != 2 or len(thresholds[0]) != n or len(thresholds[1]) != n):
+            raise ValueError("thresholds must be (bl [n], has_buf [n])")
+
+    def start(self, item_wh, total_area, rewards_list=(), first_id=0, episode_ids=None, thresholds=None):
+        """The pool is cut into one contiguous block per group; instance i's episode id is first_id + i, or episode_ids[i].
+        thresholds: (bl [n], has_buf [n]) -- instance i is ranked against that R2 threshold instead of rewards_list's."""
         item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8)
         total_area = np.ascontiguousarray(total_area, dtype=np.int32)
         buf = np.asarray(list(rewards_list), dtype=np.float64)
         self.first_id = int(first_id)
         self.n_instances = item_wh.shape[0]
+        self._check_meta(self.n_instances, episode_ids, thresholds)
         torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -228,10 +248,11 @@ class BatchedSelfPlay:
                 with torch.cuda.stream(g.stream):
                     g.refresh_weights(self.nnet)  # stem tables follow in-place weight updates
             g.eng.set_rank_buffer(buf)
-            g.eng._ck(g.eng.L.rp_set_instance_pool(g.eng.h, wh_g.shape[0], _lib._ptr(wh_g), _lib._ptr(area_g), self.first_id + lo))
+            g.eng.set_instance_pool(wh_g, area_g, self.first_id + lo)
+            self._set_meta(g, lo, hi, episode_ids, thresholds)
             g.eng._ck(g.eng.L.rp_begin_pool(g.eng.h))
 
-    def start_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, bin_w=None):
+    def start_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, bin_w=None, episode_ids=None, thresholds=None):
         """Like start(), with instance i = ItemsGenerator.items_generator(seeds[i]) of the bin_w x bin_h rectangle (default: the
         board) generated on the device (rp_set_instance_pool_seeds: bit-identical to the host generator, tests/test_gpu_rules.py);
         total area bin_w * bin_h."""
@@ -239,6 +260,7 @@ class BatchedSelfPlay:
         buf = np.asarray(list(rewards_list), dtype=np.float64)
         self.first_id = int(first_id)
         self.n_instances = seeds.shape[0]
+        self._check_meta(self.n_instances, episode_ids, thresholds)
         torch.cuda.synchronize(self.device)
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -249,6 +271,7 @@ class BatchedSelfPlay:
                     g.refresh_weights(self.nnet)
             g.eng.set_rank_buffer(buf)
             g.eng.set_instance_pool_seeds(np.ascontiguousarray(seeds[lo:hi]), bin_w or self.W, bin_h or self.H, self.first_id + lo)
+            self._set_meta(g, lo, hi, episode_ids, thresholds)
             g.eng._ck(g.eng.L.rp_begin_pool(g.eng.h))
 
     def active(self):
@@ -278,15 +301,16 @@ class BatchedSelfPlay:
                 tot[name] += val
         return tot
 
-    def run(self, item_wh, total_area, rewards_list=(), first_id=0, poll=16, max_steps=None):
+    def run(self, item_wh, total_area, rewards_list=(), first_id=0, poll=16, max_steps=None, episode_ids=None, thresholds=None):
         """Plays every instance of the pool to the end.  Returns (episode ids, outcomes, scores, moves) sorted by id,
-        plus timing / counter statistics."""
-        self.start(item_wh, total_area, rewards_list, first_id)
+        plus timing / counter statistics.  episode_ids / thresholds: see start()."""
+        self.start(item_wh, total_area, rewards_list, first_id, episode_ids, thresholds)
         return self._play_out(poll, max_steps)
 
-    def run_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, poll=16, max_steps=None, bin_w=None):
+    def run_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, poll=16, max_steps=None, bin_w=None, episode_ids=None,
+                       thresholds=None):
         """run() on device-generated instances (start_from_seeds)."""
-        self.start_from_seeds(seeds, rewards_list, first_id, bin_h, bin_w)
+        self.start_from_seeds(seeds, rewards_list, first_id, bin_h, bin_w, episode_ids, thresholds)
         return self._play_out(poll, max_steps)
 
     def _play_out(self, poll, max_steps):
