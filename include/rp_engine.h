@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 4  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async */
+#define RP_ABI_VERSION 5  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+                             5: placement trace (rp_set_trace, rp_pop_finished_packings) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -163,6 +164,18 @@ int rp_set_compact_rows(rp_ctx *ctx, int32_t enable);
 /* Switches the move rule; onehot_examples != 0 records pi as a one-hot on the played action, the greedy branch of
  * MCTS.getActionProb (greedy_a == 0, MCTS_bpp.py:43-49) that CoachBPP uses after iterStepThreshold (CoachBPP.py:132). */
 int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples);
+/* Placement trace: with enable != 0 every move played on the device -- by any rp_move_rule, rp_advance_roots included -- is recorded
+ * as (action, rows): action = item * W + column as BinPackingGame.getNextState takes it (BinPackingGame.py:58-76, item and column
+ * split at :67), rows = bit r set iff the move filled cells of bin row r.  Bin.execute_move (BinPackingLogic.py:95-109) fills the
+ * first h free row segments scanning from row 0, so the rows of one move may be non-contiguous, and fewer than h where the strip
+ * runs out; they are read off as the rows where the new root's key differs from the old one's, which costs the search nothing.
+ * When an episode ends its moves and final bin -- what the reference's display(board) prints (BinPackingGame.py:232) -- are kept
+ * next to its finished record for rp_pop_finished_packings.  Refused with RP_ERR_STATE while any slot is in the middle of an episode.
+ * The buffers are allocated on the first enable: fin_cap * (10 N + 8 H) bytes for the ring (fin_cap = max(4 G, 1024)) plus 10 G N
+ * for the running episodes -- 73 MB at 32 768 slots of 20x20 / 32 items in two contexts; with the trace off nothing is allocated and
+ * the kernels take one uniform branch.  Kernel arguments are baked into captured graphs: re-capture after switching, as after
+ * rp_set_move_rule.  Records of episodes that finished while the trace was off carry no trace: drain the ring before switching. */
+int rp_set_trace(rp_ctx *ctx, int32_t enable);
 /* Changes args.numMCTSSims for the following searches (MCTS_bpp.py:37); rp_search_step stops a slot after this many
  * simulations from its current root. */
 int rp_set_sims(rp_ctx *ctx, int32_t sims);
@@ -264,6 +277,13 @@ int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const int32_t *a
 /* Finished episodes since the last call (auto move rules): up to max_n records, oldest first. */
 int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
                     int32_t *moves_out, int64_t *n_out);
+/* rp_pop_finished plus each episode's packing (rp_set_trace): the moves CoachBPP.executeEpisode / arena_playing played through
+ * getNextState (CoachBPP.py:88-91, 262) and the board it ended on.  action_out[k][m] / rows_out[k][m] describe move m of record k
+ * (zero for m >= moves_out[k]), board_out[k][r] is row r of the final bin.  Same ring and cursor as rp_pop_finished; any output may be
+ * NULL.  RP_ERR_ARG while the trace is off. */
+int rp_pop_finished_packings(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
+                             int32_t *moves_out, uint16_t *action_out /*[max_n][N]*/, uint64_t *rows_out /*[max_n][N]*/,
+                             uint64_t *board_out /*[max_n][H]*/, int64_t *n_out);
 /* Engine counters summed over slots since create/reset: [0] simulations, [1] expansions (leaf evaluations),
  * [2] terminal returns, [3] path edges walked, [4] sum of n_valid at selected nodes, [5] sum of n_valid at
  * expanded leaves, [6] transposition links, [7] nodes created, [8] moves played, [9] episodes finished,

@@ -22,6 +22,19 @@ alternatives) and replacements of its use of OS entropy:
   * with several ranks a training step still covers `batch_size` examples: one index stream shared by all ranks, each rank
     takes every world-th index, gradients are summed (see `NNetWrapper.train_tensors`).
 `executeEpisode` keeps the reference's sequential semantics through the `MCTS` / `BinPackingGame` classes.
+
+`arena_playing(pmcts, nmcts, seeds_iter)` (CoachBPP.py:233-291) pits two networks against each other on `args.arenaCompare`
+instances drawn from `seeds_iter`, each playing greedily, and returns 1 iff mean(n_scores) >= mean(p_scores); with
+`args.arena_gate` `learn()` runs the accept / reject block the reference keeps commented out (CoachBPP.py:171-193).  Both go through
+the batched driver.  Differences from the reference:
+  * every arena game gets a fresh tree; the reference's two `MCTS` objects keep theirs across games (instances differ from game to
+    game, so a kept tree can only be revisited through states two instances share);
+  * greedy ties follow args.greedy_tie_break (the reference draws among tied maxima from the global NumPy stream, MCTS_bpp.py:45-46);
+  * the arena seeds are drawn with `random.sample` (:238-239) from OS entropy on rank 0 and broadcast, or pinned by `args.arena_seed`;
+  * instances are cut by the device generator at the current `gen.bin_height`, as self-play cuts them;
+  * the old network plays BEFORE training (its weights are the live ones then), the new one after; a network that is not the
+    driver's own plays by having its state dict copied IN PLACE into the driver's network -- the captured graphs hold the parameter
+    pointers -- which is restored afterwards.
 """
 import logging
 import os
@@ -59,6 +72,15 @@ def trim_min(scores, cap):
     return [s for s, m in zip(scores, keep) if m]
 
 
+class ArenaScores:
+    """A network's side of an arena that has been played already: the seeds drawn and its score on each.  learn() plays the old
+    network before training and hands this to arena_playing in place of `pmcts`."""
+
+    def __init__(self, seeds, scores):
+        self.seeds = [int(x) for x in seeds]
+        self.scores = np.asarray(scores, dtype=np.float64)
+
+
 class CoachBPP:
     def __init__(self, game, nnet, items_list, total_area, gen, args, saved_rewards_list=[]):
         self.game = game
@@ -78,6 +100,8 @@ class CoachBPP:
         self.iteration_scores = []  # ep_scores of every iteration, in episode order
         self._selfplay = None
         self.repair_log = []  # sequential rank buffer: per iteration rounds, episodes replayed per round, seconds, final (has_buf, bl)
+        self.last_arena = None  # dict(seeds, p_scores, n_scores, accepted) of the latest arena_playing
+        self.last_seeds_iter = []  # generator seeds of the latest self-play iteration (the arena draws from them)
 
     # ---- sequential episode, reference semantics (CoachBPP.py:50-99) --------------------------------------------------
     def executeEpisode(self, greedy=False):
@@ -130,7 +154,8 @@ class CoachBPP:
                                              edge_cap=int(_opt(self.args, "edge_cap", 0) or 0), vis_cap=int(_opt(self.args, "vis_cap", 0) or 0),
                                              max_examples=per_rank * moves_cap + 64, use_graph=bool(_opt(self.args, "use_graph", True)),
                                              groups=max(1, min(int(_opt(self.args, "groups", 2) or 2), games)),
-                                             tie_salt=_opt(self.args, "tie_salt", None), host_evaluator=_opt(self.args, "host_evaluator", None))
+                                             tie_salt=_opt(self.args, "tie_salt", None), host_evaluator=_opt(self.args, "host_evaluator", None),
+                                             record_packings=bool(_opt(self.args, "record_packings", False)))  # layouts: self._selfplay.pop_packings()
             self._selfplay_per_rank = per_rank
             self._move_mode = None
         return self._selfplay
@@ -157,6 +182,7 @@ class CoachBPP:
         args = self.args
         bin_height, seeds = self.drawIteration() if draws is None else (int(draws[0]), [int(x) for x in draws[1]])
         n_eps = len(seeds)
+        self.last_seeds_iter = list(seeds)
         self.gen.bin_height = bin_height  # :118
         self.items_total_area = self.gen.bin_height * self.gen.bin_width  # :119
         mine = rdist.shard(n_eps)
@@ -286,6 +312,69 @@ class CoachBPP:
         self.repair_log.append(record)
         return res["scores"], state["replay"], record
 
+    # ---- arena (CoachBPP.py:233-291) -----------------------------------------------------------------------------------
+    def _arena_seeds(self, seeds_iter):
+        """random.sample(seeds_iter, args.arenaCompare) (:238-239), the same on every rank."""
+        import random
+        import torch
+        k = int(self.args.arenaCompare)
+        pinned = _opt(self.args, "arena_seed", None)
+        rng = random.Random(int(pinned)) if pinned is not None else random.Random(int.from_bytes(os.urandom(8), "little"))
+        picked = rng.sample(list(seeds_iter), k)
+        if pinned is None and rdist.collectives_on():
+            t = torch.tensor(picked, dtype=torch.int64, device=self.nnet.device)
+            torch.distributed.broadcast(t, src=0)
+            picked = t.cpu().tolist()
+        return [int(x) for x in picked]
+
+    def _arena_scores(self, net, arena_seeds):
+        """Scores [len(arena_seeds)] float64, the same array on every rank, of `net` (an NNetWrapper) packing the instances of the
+        seeds greedily: sharded over the ranks like self-play, every game on a fresh tree, no training examples kept."""
+        import torch
+        from .solve import greedy_rule
+        n = len(arena_seeds)
+        sp = self._driver(max(n, int(_opt(self.args, "numEps", n) or n)))
+        own = sp.nnet
+        backup = None
+        if net is not own:  # the driver's graphs hold ITS network's parameter pointers: copy the weights in place, never swap tensors
+            backup = {k: v.detach().clone() for k, v in own.nnet.state_dict().items()}
+            own.nnet.load_state_dict({k: v.detach().to(own.device) for k, v in net.nnet.state_dict().items()})
+        try:
+            rule = greedy_rule(self.args)
+            if sp.move_rule != rule or self._move_mode is not None:
+                sp.set_move_rule(rule)
+            self._move_mode = None  # the next self-play iteration sets its own rule and targets again
+            sp.clear_examples()
+            mine = rdist.shard(n)
+            dev = self.nnet.device
+            local = torch.zeros(len(mine), dtype=torch.float64, device=dev)
+            if mine:
+                seeds_p = np.asarray([arena_seeds[k] for k in mine], dtype=np.uint32)
+                ids, _, score, _, _ = sp.run_from_seeds(seeds_p, self.rewards_list, first_id=int(mine[0]), bin_h=self.gen.bin_height, bin_w=self.gen.bin_width)
+                local[torch.as_tensor(ids.astype(np.int64) - int(mine[0]), device=dev)] = torch.as_tensor(score, device=dev)
+            sp.clear_examples()
+            return self._gather_scores(mine, local, n)
+        finally:
+            if backup is not None:
+                own.nnet.load_state_dict(backup)
+                torch.cuda.synchronize(own.device)
+
+    def arena_playing(self, pmcts, nmcts, seeds_iter):
+        """1 iff the new network's mean score over args.arenaCompare instances drawn from seeds_iter is at least the old one's
+        (:288-291).  pmcts / nmcts: `MCTS` objects (their .nnet plays) or NNetWrappers; pmcts may also be the `ArenaScores` of an
+        old network that has played already (learn() plays it before training): nmcts then plays the same seeds and nothing is drawn
+        from seeds_iter.  Leaves self.last_arena = dict(seeds, p_scores, n_scores, accepted)."""
+        net_of = lambda m: m.nnet if isinstance(m, MCTS) else m
+        if isinstance(pmcts, ArenaScores):
+            arena_seeds, p_scores = pmcts.seeds, pmcts.scores
+        else:
+            arena_seeds = self._arena_seeds(seeds_iter)
+            p_scores = self._arena_scores(net_of(pmcts), arena_seeds)
+        n_scores = self._arena_scores(net_of(nmcts), arena_seeds)
+        accepted = 1 if np.mean(n_scores) >= np.mean(p_scores) else 0
+        self.last_arena = dict(seeds=list(arena_seeds), p_scores=np.asarray(p_scores, np.float64), n_scores=np.asarray(n_scores, np.float64), accepted=accepted)
+        return accepted
+
     def learn(self):
         import time
         import torch
@@ -314,6 +403,14 @@ class CoachBPP:
             train_set = PackedReplay.cat(self.trainExamplesHistory)
             if rdist.rank() == 0:
                 self.nnet.save_checkpoint(folder=args.checkpoint, filename="temp.pth.tar")  # :172
+            gate = bool(_opt(args, "arena_gate", False))
+            pit = gate and (not self.skipFirstSelfPlay or i > 1)  # :179-184
+            arena_s = 0.0
+            if pit:  # the old network plays its arena games now, while its weights are the live ones: no weight swap later
+                t0 = time.time()
+                arena_seeds = self._arena_seeds(self.last_seeds_iter)
+                old = ArenaScores(arena_seeds, self._arena_scores(self.nnet, arena_seeds))
+                arena_s += time.time() - t0
             t0 = time.time()
             self.nnet.train_packed(train_set)  # :176 (sampling is with replacement, so no shuffle is needed)
             if self.nnet.device.type == "cuda":
@@ -321,6 +418,28 @@ class CoachBPP:
             if self.timings:
                 self.timings[-1].update(train_s=time.time() - t0, train_steps=int(getattr(self.nnet, "last_train_steps", 0)), train_examples=len(train_set),
                                         train_set_bytes=train_set.nbytes)
+            if gate:
+                t0 = time.time()
+                n_win = self.arena_playing(old, self.nnet, self.last_seeds_iter) if pit else 1  # :179-184
+                if rdist.collectives_on():
+                    torch.distributed.barrier()  # temp.pth.tar is rank 0's file
+                if n_win == 0:  # :187-189
+                    log.info("REJECTING NEW MODEL")
+                    self.nnet.load_checkpoint(folder=args.checkpoint, filename="temp.pth.tar")
+                else:  # :190-193
+                    log.info("ACCEPTING NEW MODEL")
+                    if rdist.rank() == 0:
+                        self.nnet.save_checkpoint(folder=args.checkpoint, filename="best.pth.tar")
+                arena_s += time.time() - t0
+                la = self.last_arena if pit and self.last_arena is not None else None
+                arena = {"arena accepted": int(n_win), "arena mean new": float(np.mean(la["n_scores"])) if la else None,
+                         "arena mean old": float(np.mean(la["p_scores"])) if la else None}
+                if self.metrics_log and self.metrics_log[-1].get("iteration") == i:
+                    self.metrics_log[-1].update(arena)
+                else:
+                    self.metrics_log.append(dict(arena, iteration=i))
+                if self.timings:
+                    self.timings[-1].update(arena_s=arena_s)
             if rdist.rank() == 0:
                 self.save_rewards_list()  # :196
 

@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -61,6 +61,7 @@ _SIGS = {
     "rp_set_compact_rows": (C.c_int, [_vp, _i32]),
     "rp_set_move_rule": (C.c_int, [_vp, _i32, _i32]),
     "rp_set_sims": (C.c_int, [_vp, _i32]),
+    "rp_set_trace": (C.c_int, [_vp, _i32]),
     "rp_last_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_search_step": (C.c_int, [_vp, _vp]),
     "rp_leaf_planes": (C.c_int, [_vp, _vp, _i64]),
@@ -84,6 +85,7 @@ _SIGS = {
     "rp_game_status": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rp_advance_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "rp_pop_finished": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "rp_pop_finished_packings": (C.c_int, [_vp, _i64] + [_vp] * 8),
     "rp_counters": (C.c_int, [_vp, _vp, _i32]),
     "rp_examples_count": (C.c_int, [_vp, _vp]),
     "rp_examples_tensors": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
@@ -171,6 +173,7 @@ class Engine:
             raise EngineError(rc, self.L.rp_last_error(None).decode())
         self.h = h
         self.pool_size = 0  # size of the pool set last (rp_set_instance_pool*)
+        self.trace = False  # placement trace (set_trace)
 
     def close(self):
         if getattr(self, "h", None):
@@ -277,6 +280,11 @@ class Engine:
     def set_sims(self, sims):
         self._ck(self.L.rp_set_sims(self.h, int(sims)))
         self.sims = int(sims)
+
+    def set_trace(self, on=True):
+        """Placement trace (rp_set_trace): every move's (action, filled rows) and the final bin, read with pop_finished(packings=True)."""
+        self._ck(self.L.rp_set_trace(self.h, 1 if on else 0))
+        self.trace = bool(on)
 
     def last_values(self, first=0, count=None):
         count = self.G - first if count is None else count
@@ -494,12 +502,21 @@ class Engine:
         self._ck(self.L.rp_advance_roots(self.h, first, count, _ptr(action), _ptr(ended), _ptr(score)))
         return ended, score
 
-    def pop_finished(self, max_n=1 << 20):
+    def pop_finished(self, max_n=None, packings=False):
+        """(episode ids, outcomes, scores, moves) of up to max_n finished episodes, oldest first; packings=True adds each one's
+        placement trace: actions u16 [n, N], filled-row masks u64 [n, N] and final bin rows u64 [n, H] (rp_pop_finished_packings)."""
+        if max_n is None:  # the ring holds at most max(4 G, 1024) records
+            max_n = max(4 * self.G, 1024) if packings else 1 << 20
         ids = np.empty(max_n, np.uint64); oc = np.empty(max_n, np.int32); sc = np.empty(max_n, np.float64); mv = np.empty(max_n, np.int32)
         n = _i64(0)
-        self._ck(self.L.rp_pop_finished(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), C.byref(n)))
+        if not packings:
+            self._ck(self.L.rp_pop_finished(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), C.byref(n)))
+            k = n.value
+            return ids[:k], oc[:k], sc[:k], mv[:k]
+        act = np.empty((max_n, self.N), np.uint16); rows = np.empty((max_n, self.N), np.uint64); board = np.empty((max_n, self.H), np.uint64)
+        self._ck(self.L.rp_pop_finished_packings(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), _ptr(act), _ptr(rows), _ptr(board), C.byref(n)))
         k = n.value
-        return ids[:k], oc[:k], sc[:k], mv[:k]
+        return ids[:k], oc[:k], sc[:k], mv[:k], act[:k].copy(), rows[:k].copy(), board[:k].copy()
 
     def counters(self, reset=False):
         out = np.zeros(16, np.int64)

@@ -180,6 +180,13 @@ struct DP {  // device view of a context, passed by value to every kernel
     u64 *fin_episode;
     int *fin_outcome, *fin_moves;
     double *fin_score;
+    // placement trace (rp_set_trace): NULL while it is off -- the move routine then takes one wave-uniform branch and touches nothing.
+    // A move is (action, mask of the bin rows it filled); a finished episode's moves and final bin go to the ring entry of the same index.
+    u16 *tr_action;      // [G][N] the running episode of every slot
+    u64 *tr_rows;        // [G][N]
+    u16 *fin_tr_action;  // [fin_cap][N], zero past the episode's moves
+    u64 *fin_tr_rows;    // [fin_cap][N]
+    u64 *fin_board;      // [fin_cap][H] row masks of the final bin
 };
 // the first error of a launch sequence is the one reported (later ones are usually its consequences)
 __device__ __forceinline__ void set_error(const DP &p, int code) { atomicCAS(p.error, 0, code); }
@@ -1072,6 +1079,17 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
             set_error(p, ERR_EXAMPLES_CAP);
         }
     }
+    u64 filled = 0;  // wave-uniform, like chosen_action: the episode's end below takes this move's entry from the registers
+    if (p.tr_action) {  // placement trace: the rows the move filled are those where the child's key differs from the root's
+        const int mv = p.moves[g];
+        row_t before = 0, after = 0;
+        if (lane < p.H) {
+            before = ((const row_t *)(t.key + (size_t)root * p.KW))[lane];
+            after = ((const row_t *)(t.key + (size_t)child * p.KW))[lane];
+        }
+        filled = __ballot(before != after);
+        if (lane == 0 && mv < p.N) { p.tr_action[(size_t)g * p.N + mv] = (u16)chosen_action; p.tr_rows[(size_t)g * p.N + mv] = filled; }
+    }
     if (p.reclaim) {  // everything at the old root's level is unreachable from now on
         arena_free_level(t.pa, hd.depth);
         arena_free_level(t.va, hd.depth);
@@ -1092,15 +1110,27 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
                 u32 idx = p.slot_ex[(size_t)g * p.N + q];
                 if ((long long)idx < p.max_examples) p.ex_value[idx] = ch.term;
             }
+        int idx = 0;
         if (lane == 0) {
             p.last_outcome[g] = ch.term;
             p.last_score[g] = r;
             p.phase[g] = RP_PHASE_EPISODE_DONE;
-            int idx = atomicAdd(p.fin_count, 1);
+            idx = atomicAdd(p.fin_count, 1);
             if (idx < p.fin_cap) {
                 p.fin_episode[idx] = p.episode[g]; p.fin_outcome[idx] = ch.term; p.fin_score[idx] = r; p.fin_moves[idx] = moves;
             } else {
                 set_error(p, ERR_FINISHED_CAP);
+            }
+        }
+        if (p.tr_action) {  // the episode's trace and final bin, at the ring index of its record
+            idx = __shfl(idx, 0);
+            if (idx < p.fin_cap) {
+                for (int q = lane; q < p.N; q += 64) {  // earlier moves were stored by earlier launches (a launch plays one move per slot)
+                    const bool earlier = q < moves - 1, last = q == moves - 1;
+                    p.fin_tr_action[(size_t)idx * p.N + q] = last ? (u16)chosen_action : earlier ? p.tr_action[(size_t)g * p.N + q] : (u16)0;
+                    p.fin_tr_rows[(size_t)idx * p.N + q] = last ? filled : earlier ? p.tr_rows[(size_t)g * p.N + q] : 0ull;
+                }
+                if (lane < p.H) p.fin_board[(size_t)idx * p.H + lane] = (u64)myrow;
             }
         }
     } else if (lane == 0) {
@@ -3356,6 +3386,9 @@ struct rp_ctx {
     size_t lds_per_cu = 160 * 1024;
     int compact_rows = 0;             // rp_set_compact_rows: rp_search_step(ctx, NULL) lists the waiting slots on the device too
     const int *nn_rows_dev = nullptr;  // row limit of the rp_nn_* stage kernels (eval_count) while compact rows are on
+    // placement trace buffers (rp_set_trace): allocated on the first enable, kept until destroy; the DP holds them only while it is on
+    u16 *tr_action = nullptr, *fin_tr_action = nullptr;
+    u64 *tr_rows = nullptr, *fin_tr_rows = nullptr, *fin_board = nullptr;
 };
 
 static std::string g_create_error;
@@ -3807,6 +3840,33 @@ extern "C" int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_e
     ctx->d.move_rule = move_rule;
     ctx->d.onehot_examples = onehot_examples ? 1 : 0;
     ctx->cfg.move_rule = move_rule;
+    return RP_OK;
+}
+
+extern "C" int rp_set_trace(rp_ctx *ctx, int32_t enable) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_trace: bad argument");
+    DP &d = ctx->d;
+    {   // not while episodes are being played: their first moves would be missing from the trace
+        std::vector<int> ph((size_t)d.G);
+        HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int g = 0; g < d.G; ++g)
+            if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY)
+                return fail(ctx, RP_ERR_STATE, "rp_set_trace: slot %d is in the middle of an episode; switch the trace between pools", g);
+    }
+    if (enable && !ctx->tr_action) {
+        const size_t G = (size_t)d.G, N = (size_t)d.N, F = (size_t)d.fin_cap;
+        // the context takes the five buffers together or not at all: an allocation that fails leaves the trace off and unallocated
+        // (what was obtained before it stays in ctx->allocs and is freed with the context)
+        u16 *ta = nullptr, *fa = nullptr;
+        u64 *tr = nullptr, *fr = nullptr, *fb = nullptr;
+        ALLOC(ctx, ta, G * N); ALLOC(ctx, tr, G * N);
+        ALLOC(ctx, fa, F * N); ALLOC(ctx, fr, F * N); ALLOC(ctx, fb, F * (size_t)d.H);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->tr_action = ta; ctx->tr_rows = tr; ctx->fin_tr_action = fa; ctx->fin_tr_rows = fr; ctx->fin_board = fb;
+    }
+    if (enable) { d.tr_action = ctx->tr_action; d.tr_rows = ctx->tr_rows; d.fin_tr_action = ctx->fin_tr_action; d.fin_tr_rows = ctx->fin_tr_rows; d.fin_board = ctx->fin_board; }
+    else { d.tr_action = nullptr; d.tr_rows = nullptr; d.fin_tr_action = nullptr; d.fin_tr_rows = nullptr; d.fin_board = nullptr; }
     return RP_OK;
 }
 
@@ -4290,9 +4350,8 @@ extern "C" int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const
     return check_device_error(ctx);
 }
 
-extern "C" int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
-                               int32_t *moves_out, int64_t *n_out) {
-    if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished: bad argument");
+static int pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out, int32_t *moves_out,
+                        uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, int64_t *n_out) {
     const DP &d = ctx->d;
     int cnt = 0;
     HIPCHK(ctx, hipMemcpyAsync(&cnt, d.fin_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -4306,6 +4365,9 @@ extern "C" int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_
     if (outcome_out) HIPCHK(ctx, hipMemcpyAsync(outcome_out, d.fin_outcome + off, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (score_out) HIPCHK(ctx, hipMemcpyAsync(score_out, d.fin_score + off, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (moves_out) HIPCHK(ctx, hipMemcpyAsync(moves_out, d.fin_moves + off, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (action_out) HIPCHK(ctx, hipMemcpyAsync(action_out, d.fin_tr_action + off * d.N, n * d.N * sizeof(u16), hipMemcpyDeviceToHost, ctx->stream));
+    if (rows_out) HIPCHK(ctx, hipMemcpyAsync(rows_out, d.fin_tr_rows + off * d.N, n * d.N * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    if (board_out) HIPCHK(ctx, hipMemcpyAsync(board_out, d.fin_board + off * d.H, n * d.H * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->fin_popped += n;
     if (ctx->fin_popped == cnt) {  // ring drained: rewind
@@ -4314,6 +4376,19 @@ extern "C" int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_
         ctx->fin_popped = 0;
     }
     return RP_OK;
+}
+
+extern "C" int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
+                               int32_t *moves_out, int64_t *n_out) {
+    if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished: bad argument");
+    return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, nullptr, nullptr, nullptr, n_out);
+}
+
+extern "C" int rp_pop_finished_packings(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
+                                        int32_t *moves_out, uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, int64_t *n_out) {
+    if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_packings: bad argument");
+    if (!ctx->d.tr_action) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_packings: the placement trace is off (rp_set_trace(ctx, 1) before the pool begins)");
+    return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out);
 }
 
 extern "C" int rp_set_instance_pool(rp_ctx *ctx, int64_t n_instances, const uint8_t *item_wh, const int32_t *total_area, uint64_t first_id) {

@@ -36,6 +36,8 @@ class _Group:
                                vis_cap=owner.vis_cap, reclaim=1 if owner.reclaim else 0)
         self.eng.set_step_cap(owner.step_cap)
         self.eng.set_compact_rows(owner.compact_rows)
+        if owner.record_packings:
+            self.eng.set_trace(True)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         if self.use_stem:  # the engine computes the first conv + pool itself: no plane tensor at all
@@ -99,8 +101,10 @@ class _Group:
 class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
-                 tie_salt=None, host_evaluator=None):
-        """host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
+                 tie_salt=None, host_evaluator=None, record_packings=False):
+        """record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
+        return and the finished episodes' layouts are collected for pop_packings().
+        host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
         eagerly with one host round trip each.  tie_salt: salt of the deterministic `r == bl` tie (default: derived from seed)."""
         self.game, self.nnet, self.args = game, nnet, args
@@ -116,6 +120,9 @@ class BatchedSelfPlay:
         self.compact_rows = bool(compact_rows)  # evaluator rows = the waiting slots only, listed on the device (rp_set_compact_rows)
         self.max_examples_per_group = (int(max_examples) + groups - 1) // groups if max_examples else 0
         self.tie_salt, self.host_evaluator = tie_salt, host_evaluator
+        self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
+        self._packings = []
+        self._pool_items = None
         self.use_graph = bool(use_graph) and host_evaluator is None
         self.use_stem = bool(use_stem)
         self.fuse_elementwise = bool(fuse_elementwise) and self.use_stem
@@ -200,6 +207,14 @@ class BatchedSelfPlay:
         self.move_rule = move_rule
         self.invalidate_graph()
 
+    def set_record_packings(self, on=True):
+        """Switches the placement trace of every group between pools (refused while episodes are being played); re-captures the waves."""
+        for g in self.groups:
+            g.eng.set_trace(on)
+        self.record_packings = bool(on)
+        self._packings = []
+        self.invalidate_graph()
+
     # ---- whole pools -------------------------------------------------------------------------------
     def _blocks(self, n):
         """Contiguous block of the pool per group: [(lo, hi)]; instance i has episode id first_id + i."""
@@ -238,6 +253,7 @@ class BatchedSelfPlay:
         self.first_id = int(first_id)
         self.n_instances = item_wh.shape[0]
         self._check_meta(self.n_instances, episode_ids, thresholds)
+        self._pool_items = (episode_ids, item_wh) if self.record_packings else None
         torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -261,6 +277,7 @@ class BatchedSelfPlay:
         self.first_id = int(first_id)
         self.n_instances = seeds.shape[0]
         self._check_meta(self.n_instances, episode_ids, thresholds)
+        self._pool_items = (episode_ids, (seeds, bin_w or self.W, bin_h or self.H)) if self.record_packings else None
         torch.cuda.synchronize(self.device)
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -282,13 +299,39 @@ class BatchedSelfPlay:
         return n
 
     def pop_finished(self):
-        """(episode ids, outcomes, scores, moves) of the episodes finished since the last call, sorted by id."""
+        """(episode ids, outcomes, scores, moves) of the episodes finished since the last call, sorted by id.  With record_packings
+        their layouts are set aside for pop_packings()."""
         parts = []
         for g in self.groups:
-            ids, oc, sc, mv = g.eng.pop_finished()
-            parts.append((ids.astype(np.int64), oc, sc, mv))
+            rec = g.eng.pop_finished(packings=self.record_packings)
+            parts.append((rec[0].astype(np.int64),) + tuple(rec[1:]))
         ids = np.concatenate([p[0] for p in parts]); order = np.argsort(ids, kind="stable")
-        return tuple(np.concatenate([p[j] for p in parts])[order] for j in range(4))
+        out = tuple(np.concatenate([p[j] for p in parts])[order] for j in range(len(parts[0])))
+        if self.record_packings and len(ids):
+            self._keep_packings(*out)
+        return out[:4]
+
+    def _keep_packings(self, ids, outcome, score, moves, action, rows, board):
+        """Packing records of finished episodes of the current pool (their item sizes come from it)."""
+        from .solve import Packing
+        if self._pool_items is None:
+            raise RuntimeError("episodes finished before a pool was started with record_packings on")
+        episode_ids, items = self._pool_items
+        if isinstance(items, tuple):  # a pool of generator seeds: the same device generator gives the sizes back
+            seeds, bin_w, bin_h = items
+            items = self.eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
+            self._pool_items = (episode_ids, items)
+        pool_ids = self.first_id + np.arange(self.n_instances, dtype=np.int64) if episode_ids is None else np.asarray(episode_ids, dtype=np.int64)
+        index = {int(e): k for k, e in enumerate(pool_ids)}
+        for k in range(len(ids)):
+            m = int(moves[k])
+            self._packings.append(Packing(int(ids[k]), self.W, items[index[int(ids[k])]], action[k, :m], rows[k, :m], board[k], int(outcome[k]), float(score[k])))
+
+    def pop_packings(self):
+        """solve.Packing of every episode that finished (and was popped: run() does) since the last call, sorted by episode id."""
+        out = sorted(self._packings, key=lambda p: p.episode_id)
+        self._packings = []
+        return out
 
     def arena_peak(self):
         peaks = [g.eng.arena_peak() for g in self.groups]
