@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rp_engine.h"
@@ -2943,6 +2944,186 @@ __global__ void __launch_bounds__(256, 2) k_resstage32(const float *__restrict__
     }
 }
 
+// Position-major variant for 3x3 and 5x5 images.  k_resstage32's tiles mix the pixel positions of several leaves, so every
+// tile takes all nine taps although a tap of a border pixel multiplies weights with zero padding (3x3: 32 of 81 (pixel, tap) pairs,
+// 5x5: 56 of 225), and its tiles are not full (45 of 48, 75 of 80 columns).  Here a tile is ONE pixel position of SIXTEEN consecutive
+// leaves (lane n = leaf), so "input position p + tap lies outside the image" is a compile-time property of the tile and those MFMAs
+// are not issued at all: 49 instead of 86.4 sixteen-column tile-taps per leaf and convolution at 3x3, 169 instead of 240 at 5x5.  Every
+// accumulator still sums its taps in r32_conv_t's order (tap, half h, j) from the same fragments and the same four channels 8 g + 4 h + j
+// per instruction; the instructions left out only ever added w * 0, so the results are the same bits up to the sign of a zero.
+//   S = 3: a wave owns 16 leaves, all nine positions (72 accumulator + 72 skip registers), image wave-local: lds_sync().
+//   S = 5: a workgroup owns 16 leaves, its four waves share the image and own 5 / 5 / 7 / 8 positions with 42 / 42 / 43 / 42 (position,
+//          tap) pairs -- four different instruction streams (ROLE), the four convolutions a runtime loop; LDS-only barriers between a
+//          convolution's reads and the in-place writes of its result, as in k_resstage32_wg.
+// LDS image: [position][leaf][32 floats] without borders; channel quad Q of leaf n sits in slot Q ^ pm_swz(n), folded into the lane's
+// four base addresses, so every operand address is base + a compile-time offset (the ds_read immediate) -- no VALU per read.  With
+// pm_swz the sixteen lanes of each ds_read_b128 lane group and the eight of each ds_write_b128 group fall on different banks.
+__host__ __device__ constexpr int pm_swz(int n) { return (((n >> 1) & 1) | (((n >> 2) & 1) * 6)) ^ ((n & 1) * 4); }
+__host__ __device__ constexpr int pm_in_pos(int S, int p, int tap) {  // input position of output position p under `tap`, -1 outside the image
+    const int r = p / S + tap / 3 - 1, c = p % S + tap % 3 - 1;
+    return (r >= 0 && r < S && c >= 0 && c < S) ? r * S + c : -1;
+}
+__host__ __device__ constexpr int pm_role_pos(int S, int role, int i) {  // i-th output position of a wave role, -1 past its last
+    if (S == 3) return i < 9 ? i : -1;
+    // 5x5: interior 6 7 8 11 12 13 16 17 18 (9 taps), corners 0 4 20 24 (4 taps), the other twelve are edges (6 taps)
+    constexpr int t[4][8] = {{6, 7, 11, 12, 1, -1, -1, -1}, {8, 13, 17, 18, 23, -1, -1, -1}, {16, 2, 3, 5, 9, 10, 0, -1}, {14, 15, 19, 21, 22, 4, 20, 24}};
+    return i < 8 ? t[role][i] : -1;
+}
+struct PmList {  // a role's (half-tap s = 2 tap + h, own position index k, input position q) in execution order
+    int n, np, ok;
+    int pos[9];
+    signed char s[100], k[100], q[100];
+};
+constexpr PmList pm_make_list(int S, int role) {
+    PmList L{};
+    while (L.np < 9 && pm_role_pos(S, role, L.np) >= 0) { L.pos[L.np] = pm_role_pos(S, role, L.np); ++L.np; }
+    L.ok = 1;
+    for (int s = 0; s < 18; ++s) {
+        int cnt = 0;
+        for (int k = 0; k < L.np; ++k) {
+            const int q = pm_in_pos(S, L.pos[k], s / 2);
+            if (q < 0) continue;
+            L.s[L.n] = (signed char)s; L.k[L.n] = (signed char)k; L.q[L.n] = (signed char)q; ++L.n; ++cnt;
+        }
+        if (cnt == 0) L.ok = 0;  // the weight stream is advanced by a half-tap's first entry: every half-tap needs one
+    }
+    return L;
+}
+template <int S, int ROLE> struct PmTab { static constexpr PmList L = pm_make_list(S, ROLE); };
+static_assert(PmTab<3, 0>::L.n == 98 && PmTab<3, 0>::L.ok, "3x3: 49 (position, tap) pairs");
+static_assert(PmTab<5, 0>::L.n + PmTab<5, 1>::L.n + PmTab<5, 2>::L.n + PmTab<5, 3>::L.n == 2 * 169 && PmTab<5, 0>::L.np + PmTab<5, 1>::L.np + PmTab<5, 2>::L.np + PmTab<5, 3>::L.np == 25 &&
+              PmTab<5, 0>::L.ok && PmTab<5, 1>::L.ok && PmTab<5, 2>::L.ok && PmTab<5, 3>::L.ok, "5x5: 169 pairs over four waves");
+template <class F, int... I> __device__ __forceinline__ void pm_for_(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void pm_for(F &&f) { pm_for_(f, std::make_integer_sequence<int, N>{}); }
+template <int S> __device__ __forceinline__ void pm_sync() {
+    if constexpr (S == 3) lds_sync(); else lds_barrier();
+}
+#define PM_IMG_FLOATS(S) ((S) * (S) * 16 * 32)
+template <int S, int ROLE>
+__device__ __forceinline__ void pm_body(const float *__restrict__ x, const float *__restrict__ frag, float *__restrict__ out, float *__restrict__ out_relu, long long B,
+                                        long long leaf0, long long stride_leaves, const float *sbias, float *img) {
+    using T = PmTab<S, ROLE>;
+    constexpr int NP = T::L.np, NE = T::L.n, PIX = S * S, CONV_BYTES = 9 * 32 * 32 * 4;
+    const int lane = lane_id(), n = lane & 15, g = lane >> 4, sw = pm_swz(n);
+    // the lane's leaf row: operand quads 2 g + h (input channels 8 g + 4 h ..), result quads g and 4 + g (output channels 16 mt + 4 g ..)
+    const float *rb0 = img + n * 32 + 4 * ((2 * g) ^ sw), *rb1 = img + n * 32 + 4 * ((2 * g + 1) ^ sw);
+    float *wb0 = img + n * 32 + 4 * (g ^ sw), *wb1 = img + n * 32 + 4 * ((4 + g) ^ sw);
+    const int voff = lane * 16, xoff = n * (PIX * 128) + g * 16;  // byte offsets: weight piece; (leaf n, channel quad g) of a task's x / out
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)frag, 0, 4 * CONV_BYTES, RS_BUF_FLAGS);
+    f32x4 xs[NP][2], acc[NP][2], wq[3][2], bq[3];
+    wq[0][0] = rs_load_b(frs, voff, 0); wq[0][1] = rs_load_b(frs, voff, 1024);
+    wq[1][0] = rs_load_b(frs, voff, 2048); wq[1][1] = rs_load_b(frs, voff, 3072);
+    auto b_read = [&](auto E) {  // operand of entry E: (input position, half) of this lane's leaf and channel group
+        constexpr int e = decltype(E)::value, off = T::L.q[e] * 512;
+        return *(const f32x4 *)(((T::L.s[e] & 1) ? rb1 : rb0) + off);
+    };
+    for (; leaf0 < B; leaf0 += stride_leaves) {
+        const int nbytes = (int)(B - leaf0 < 16 ? B - leaf0 : 16) * PIX * 128;  // leaves past B: loads return zeros, stores are dropped
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)leaf0 * PIX * 32), 0, nbytes, RS_BUF_FLAGS);
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value, p = T::L.pos[k];
+            xs[k][0] = rs_load_x(xrs, xoff, p * 128); xs[k][1] = rs_load_x(xrs, xoff, p * 128 + 64);
+        });
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value, p = T::L.pos[k];
+            *(f32x4 *)(wb0 + p * 512) = rs_relu(xs[k][0]); *(f32x4 *)(wb1 + p * 512) = rs_relu(xs[k][1]);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        pm_sync<S>();
+#pragma unroll 1
+        for (int kc = 0; kc < 4; ++kc) {  // block 0 conv0, conv1 (+ skip x), block 1 conv0, conv1 (+ skip y1)
+            const int fbase = kc * CONV_BYTES, fnext = ((kc + 1) & 3) * CONV_BYTES;
+            pm_for<NP>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                acc[k][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[k][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            });
+            bq[0] = b_read(std::integral_constant<int, 0>{}); bq[1] = b_read(std::integral_constant<int, 1>{});
+            pm_for<NE>([&](auto E) {
+                constexpr int e = decltype(E)::value, s = T::L.s[e], k = T::L.k[e];
+                if constexpr (e == 0 || T::L.s[e > 0 ? e - 1 : 0] != s) {  // first entry of half-tap s: request the fragments of half-tap s + 2
+                    constexpr int s2 = s + 2;
+                    const int off = s2 < 18 ? fbase + s2 * 2048 : fnext + (s2 - 18) * 2048;
+                    wq[s2 % 3][0] = rs_load_b(frs, voff, off); wq[s2 % 3][1] = rs_load_b(frs, voff, off + 1024);
+                }
+                if constexpr (e + 2 < NE) bq[(e + 2) % 3] = b_read(std::integral_constant<int, (e + 2 < NE ? e + 2 : 0)>{});
+                const f32x4 w0 = wq[s % 3][0], w1 = wq[s % 3][1], b = bq[e % 3];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[k][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[j], b[j], acc[k][0], 0, 0, 0);
+                    acc[k][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[j], b[j], acc[k][1], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            pm_sync<S>();  // every wave has read the image: the results may overwrite it
+            const f32x4 ba = *(const f32x4 *)(sbias + 32 * kc + 4 * g), bb = *(const f32x4 *)(sbias + 32 * kc + 16 + 4 * g);
+            if (kc < 3) {  // one position at a time (sched_barrier): left alone the scheduler forms all 2 NP results first, 72 more registers
+                if (kc == 1)  // y1 = conv + bias + x, kept as block 1's skip operand
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value, p = T::L.pos[k];
+                        xs[k][0] = (acc[k][0] + ba) + xs[k][0]; xs[k][1] = (acc[k][1] + bb) + xs[k][1];
+                        *(f32x4 *)(wb0 + p * 512) = rs_relu(xs[k][0]); *(f32x4 *)(wb1 + p * 512) = rs_relu(xs[k][1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                else
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value, p = T::L.pos[k];
+                        *(f32x4 *)(wb0 + p * 512) = rs_relu(acc[k][0] + ba); *(f32x4 *)(wb1 + p * 512) = rs_relu(acc[k][1] + bb);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                pm_sync<S>();
+            } else {
+                const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)leaf0 * PIX * 32), 0, nbytes, RS_BUF_FLAGS);
+                pm_for<NP>([&](auto K) {  // as k_resstage32: the results replace the accumulators, relu(result) goes out in a pass of its own
+                    constexpr int k = decltype(K)::value, p = T::L.pos[k];
+                    acc[k][0] = (acc[k][0] + ba) + xs[k][0]; acc[k][1] = (acc[k][1] + bb) + xs[k][1];
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[k][0]), ors, xoff, p * 128, RS_STREAM_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[k][1]), ors, xoff, p * 128 + 64, RS_STREAM_AUX);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                if (out_relu != nullptr) {  // uniform: relu(result) for the flatten -> hidden_fc path
+                    const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(out_relu + (size_t)leaf0 * PIX * 32), 0, nbytes, RS_BUF_FLAGS);
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value, p = T::L.pos[k];
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[k][0])), rrs, xoff, p * 128, RS_STREAM_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[k][1])), rrs, xoff, p * 128 + 64, RS_STREAM_AUX);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                }
+            }
+        }
+    }
+}
+// S = 3: a wave per task of 16 leaves (grid of workgroups of 4 waves, persistent); S = 5: a workgroup per task.  frag / bias as k_resstage32.
+template <int S>
+__global__ void __launch_bounds__(256, 2) k_resstage32_pm(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
+                                                          float *__restrict__ out, float *__restrict__ out_relu, long long B, const int *__restrict__ nrows_dev) {
+    extern __shared__ __attribute__((aligned(16))) float rb_lds[];
+    const int wv = wave_in_block();
+    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    float *sbias = rb_lds;  // [4][32]
+    if constexpr (S == 3) {
+        if ((long long)blockIdx.x * 64 >= B) return;
+        for (int i = threadIdx.x; i < 128; i += blockDim.x) sbias[i] = bias[i];
+        __syncthreads();
+        const long long leaf0 = ((long long)blockIdx.x * 4 + wv) * 16;
+        if (leaf0 >= B) return;
+        pm_body<3, 0>(x, frag, out, out_relu, B, leaf0, (long long)gridDim.x * 64, sbias, rb_lds + 128 + (size_t)wv * PM_IMG_FLOATS(3));
+    } else {
+        if ((long long)blockIdx.x * 16 >= B) return;
+        for (int i = threadIdx.x; i < 128; i += blockDim.x) sbias[i] = bias[i];
+        __syncthreads();
+        const long long leaf0 = (long long)blockIdx.x * 16, stride = (long long)gridDim.x * 16;  // the same tasks for the four waves: uniform barriers
+        float *img = rb_lds + 128;
+        switch (wv) {
+            case 0: pm_body<5, 0>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+            case 1: pm_body<5, 1>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+            case 2: pm_body<5, 2>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+            default: pm_body<5, 3>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+        }
+    }
+}
+
 // Entry of a 32-channel stage (ConvSequence.conv + max_pool2d(3, 2, 1), BinpackingNNet.py:34,39-40): 3x3 convolution
 // CIN -> 32 channels over the pixels of IMGW consecutive leaves (same transposed MFMA stream as above), bias, then the 3x3 / stride-2
 // max-pool.  Round 3: the padded images have a pixel stride of 36 floats for either CIN, and the convolution output + bias (32
@@ -3431,8 +3612,9 @@ template <typename T> static int dev_alloc(rp_ctx *ctx, T **out, size_t n, bool 
 // ceil(tasks / waves) rounds of nt pixel tiles.  Among the group sizes that fit LDS, take the one with the fewest tile-rounds -- for
 // all B rows and, weighted 3 : 1, for the ~92 % of them that hold a leaf in an average wave (3x3 images: 6 leaves = 4 tiles x 3
 // rounds, 5 leaves = 3 tiles x 3 rounds: a tenth less time at 30 000 leaves).
+#define STAGE_WAVES 2048
 static int pick_leaves_per_wave(long long B, int PIX, int imgw_max) {
-    const long long waves = 2048, typical = std::max<long long>(1, (long long)(0.92 * (double)B));
+    const long long waves = STAGE_WAVES, typical = std::max<long long>(1, (long long)(0.92 * (double)B));
     long long best = -1;
     int pick = std::max(1, imgw_max);
     for (int k = std::max(1, imgw_max); k >= 1; --k) {
@@ -3443,6 +3625,37 @@ static int pick_leaves_per_wave(long long B, int PIX, int imgw_max) {
     }
     return pick;
 }
+
+// The same measure for a fixed group size: rounds of `units` resident waves (or workgroups) over tasks of k leaves, all rows + 3 x the
+// typical rows.
+static long long pm_rounds_cost(long long B, int k, long long units) {
+    const long long typical = std::max<long long>(1, (long long)(0.92 * (double)B));
+    auto rounds = [&](long long rows) { const long long tasks = (rows + k - 1) / k; return (tasks + units - 1) / units; };
+    return rounds(B) + 3 * rounds(typical);
+}
+// k_resstage32's plan for images of at most 80 pixels: leaves per wave, pixel tiles, LDS bytes of a workgroup of four waves.
+static size_t r32_wave_lds(int H, int W, int k) { return ((size_t)16 * ((k * H * W + 15) / 16) + 128 + 4 * ((size_t)k * r32_imgp(H, W) + 1) * r32_ps(32)) * sizeof(float); }
+static void r32_wave_plan(long long B, int H, int W, int *imgw, int *nt) {
+    const int PIX = H * W;
+    int imgw_max = 80 / PIX;                                                   // leaves per wave: at most 5 pixel tiles of 16
+    while (imgw_max > 1 && r32_wave_lds(H, W, imgw_max) > 78 * 1024) --imgw_max;  // two workgroups per CU
+    *imgw = pick_leaves_per_wave(B, PIX, imgw_max);
+    *nt = (*imgw * PIX + 15) / 16;
+}
+// k_resstage32 or k_resstage32_pm for a 3x3 / 5x5 launch of B rows: tile-taps of a wave per round x rounds.  Old: nt tiles x 9 taps over
+// STAGE_WAVES waves; new: 49 (position, tap) pairs over the waves at 3x3, 43 (the busiest wave role) over STAGE_WAVES / 4 workgroups at
+// 5x5.  Tasks of sixteen leaves quantise badly for small batches (c2: 4 096 leaves = 256 tasks): those keep the old kernel.
+static bool stage32_pm_cheaper(long long B, int H, int W) {
+    if (H != W || (H != 3 && H != 5) || B <= 0) return false;
+    int imgw, nt;
+    r32_wave_plan(B, H, W, &imgw, &nt);
+    const long long cost_old = pm_rounds_cost(B, imgw, STAGE_WAVES) * nt * 9;
+    const long long cost_pm = H == 3 ? pm_rounds_cost(B, 16, STAGE_WAVES) * 49 : pm_rounds_cost(B, 16, STAGE_WAVES / 4) * 43;
+    return cost_pm < cost_old;
+}
+// For the host-side tests of the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
+extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) { return stage32_pm_cheaper(B, H, W) ? 1 : 0; }
+extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
 
 // Leaves per WORKGROUP for the _wg stage kernels.  A CU works through its workgroups' pixel tiles at a fixed rate, so a launch takes
 // (workgroups on the busiest CU) x (tile slots of a workgroup = waves x tiles per wave): few large groups fill their tiles best but
@@ -4219,16 +4432,31 @@ extern "C" int rp_nn_resstage32(rp_ctx *ctx, const float *x_dev, const float *fr
         HIPCHK(ctx, hipGetLastError());
         return RP_OK;
     }
-    const size_t img_pixels = (size_t)r32_imgp(H, W);
-    auto lds_bytes = [&](int k) { return ((size_t)16 * ((k * PIX + 15) / 16) + 128 + 4 * (k * img_pixels + 1) * r32_ps(32)) * sizeof(float); };
-    int imgw_max = 80 / PIX;                                       // leaves per wave: at most 5 pixel tiles of 16
-    while (imgw_max > 1 && lds_bytes(imgw_max) > 78 * 1024) --imgw_max;  // two workgroups per CU
-    const int imgw = pick_leaves_per_wave(B, PIX, imgw_max);
-    const int nt = (imgw * PIX + 15) / 16;
-    const size_t lds = lds_bytes(imgw);
+    int imgw, nt;
+    r32_wave_plan(B, H, W, &imgw, &nt);
+    static const int rs32_wgs = getenv("RP_STAGE32_WGS") ? atoi(getenv("RP_STAGE32_WGS")) : 2;  // resident workgroups per CU (experiments)
+    if (H == W && (H == 3 || H == 5)) {  // position-major kernels (k_resstage32_pm)
+        const char *pm_env = getenv("RP_STAGE32_PM");  // 0: never, 1: always (read at every call: one process can run both)
+        const int pm_force = pm_env ? atoi(pm_env) : -1;
+        if (pm_force == 1 || (pm_force != 0 && stage32_pm_cheaper(B, H, W))) {
+            const size_t lds_pm = (128 + (size_t)(H == 3 ? 4 : 1) * PM_IMG_FLOATS(H)) * sizeof(float);
+            const long long tasks_pm = (B + 15) / 16, wgs = H == 3 ? (tasks_pm + 3) / 4 : tasks_pm;
+            const int per_cu_pm = (int)std::max<size_t>(1, std::min<size_t>((size_t)rs32_wgs, ctx->lds_per_cu / lds_pm));
+            const dim3 grid_pm((unsigned)std::min<long long>(wgs, (long long)ctx->n_cu * per_cu_pm)), block_pm(256);  // persistent
+            if (H == 3) {
+                const int rc_ = allow_lds(ctx, (const void *)k_resstage32_pm<3>, lds_pm, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_;
+                hipLaunchKernelGGL(k_resstage32_pm<3>, grid_pm, block_pm, lds_pm, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, ctx->nn_rows_dev);
+            } else {
+                const int rc_ = allow_lds(ctx, (const void *)k_resstage32_pm<5>, lds_pm, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_;
+                hipLaunchKernelGGL(k_resstage32_pm<5>, grid_pm, block_pm, lds_pm, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, ctx->nn_rows_dev);
+            }
+            HIPCHK(ctx, hipGetLastError());
+            return RP_OK;
+        }
+    }
+    const size_t lds = r32_wave_lds(H, W, imgw);
     if (lds > ctx->lds_per_cu) return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: a %dx%d image needs %zu bytes of LDS per workgroup, the device has %zu per CU", H, W, lds, ctx->lds_per_cu);
     const long long tasks = (B + imgw - 1) / imgw;
-    static const int rs32_wgs = getenv("RP_STAGE32_WGS") ? atoi(getenv("RP_STAGE32_WGS")) : 2;  // resident workgroups per CU (experiments)
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)rs32_wgs, ctx->lds_per_cu / lds));
     const dim3 grid((unsigned)std::min<long long>((tasks + 3) / 4, (long long)ctx->n_cu * per_cu)), block(256);  // persistent waves
 #define RS_LAUNCH(NT_)                                                                                                                              \
