@@ -3653,9 +3653,6 @@ static bool stage32_pm_cheaper(long long B, int H, int W) {
     const long long cost_pm = H == 3 ? pm_rounds_cost(B, 16, STAGE_WAVES) * 49 : pm_rounds_cost(B, 16, STAGE_WAVES / 4) * 43;
     return cost_pm < cost_old;
 }
-// For the host-side tests of the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
-extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) { return stage32_pm_cheaper(B, H, W) ? 1 : 0; }
-extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
 
 // Leaves per WORKGROUP for the _wg stage kernels.  A CU works through its workgroups' pixel tiles at a fixed rate, so a launch takes
 // (workgroups on the busiest CU) x (tile slots of a workgroup = waves x tiles per wave): few large groups fill their tiles best but
@@ -3666,6 +3663,145 @@ static long long wg_group_cost(long long B, int k, int tile_slots, int n_cu) {
     auto rounds = [&](long long rows) { const long long tasks = (rows + k - 1) / k; return (tasks + n_cu - 1) / n_cu; };
     return (rounds(B) + 3 * rounds(typical)) * tile_slots;
 }
+
+// What one stage launch looks like, from the shape, the device figures and the knobs alone (no rp_ctx, no environment, no HIP call):
+// the kernel family and its template arguments (nt tiles per wave, waves, input channels, tail blocks; k_resstage32_pm: nt = the S * S
+// pixel positions), the leaves per wave or workgroup, the wave_floats argument of the convpool kernels, LDS bytes, grid and block.
+enum { FAM_NONE, FAM_RS16, FAM_RS16_WG, FAM_RS32, FAM_RS32_WG, FAM_RS32_PM, FAM_CP, FAM_CP_WG };
+enum { PLAN_OK, PLAN_BAD_SHAPE, PLAN_NO_LDS };
+struct StagePlan { int family, nt, waves, cin, tail, imgw, wave_floats; size_t lds; unsigned grid, block; };
+struct StageDevice { int n_cu; size_t lds_per_cu; };
+struct StageKnobs { int wgs, tail, pm; };  // resident workgroups per CU; tail blocks on / off; position-major 0: never, 1: always, -1: where cheaper
+
+// persistent grid: the work items, at most the workgroups that are resident at once (wgs per CU, fewer where LDS holds fewer)
+static unsigned stage_grid(long long work, const StageDevice &dev, size_t lds, int wgs) {
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)wgs, dev.lds_per_cu / lds));
+    return (unsigned)std::min<long long>(work, (long long)dev.n_cu * per_cu);
+}
+// the wave kernels: four waves per workgroup, imgw leaves in nt tiles per wave; nt == 7 with a tail of 1 to 4 pixels runs <6, true>
+static int plan_waves(StagePlan *p, long long B, int PIX, int imgw, size_t lds, const StageDevice &dev, int wgs, bool tail_ok) {
+    p->imgw = imgw; p->nt = (imgw * PIX + 15) / 16; p->waves = 4; p->lds = lds; p->block = 256;
+    if (lds > dev.lds_per_cu) return PLAN_NO_LDS;
+    p->grid = stage_grid(((B + imgw - 1) / imgw + 3) / 4, dev, lds, wgs);
+    const int tail_px = (imgw * PIX) & 15;
+    if (tail_ok && p->nt == 7 && tail_px >= 1 && tail_px <= 4) { p->nt = 6; p->tail = 1; }  // six tiles + the 4x4x1 tail blocks (10x10: 96 + 4)
+    return PLAN_OK;
+}
+// the _wg kernels with several leaves per workgroup: the group size of least wg_group_cost among those within max_px pixels (tiles of 16,
+// dealt to 4 waves, to 8 above 16 tiles) whose LDS fits; two workgroups per CU
+template <class LdsOf> static int plan_wg_group(StagePlan *p, long long B, int PIX, int max_px, const StageDevice &dev, LdsOf lds_of) {
+    long long best = -1;
+    for (int k = 1; k * PIX <= max_px && lds_of(k) <= dev.lds_per_cu; ++k) {
+        const int tk = (k * PIX + 15) / 16, wk = tk > 16 ? 8 : 4, ntk = (tk + wk - 1) / wk;
+        const long long cost = wg_group_cost(B, k, wk * ntk, dev.n_cu);
+        if (best < 0 || cost < best) { best = cost; p->imgw = k; p->nt = ntk; p->waves = wk; }
+    }
+    if (best < 0) return PLAN_NO_LDS;  // not even one image (lds stays 0)
+    p->lds = lds_of(p->imgw); p->block = 64 * p->waves;
+    p->grid = stage_grid((B + p->imgw - 1) / p->imgw, dev, p->lds, 2);
+    return PLAN_OK;
+}
+
+static int plan_resstage16(StagePlan *p, long long B, int H, int W, const StageDevice &dev, const StageKnobs &kn) {
+    *p = StagePlan{};
+    if (B < 0 || H < 1 || W < 1 || H * W > 640) return PLAN_BAD_SHAPE;
+    if (B == 0) return PLAN_OK;  // nothing to launch
+    const int PIX = H * W;
+    p->cin = 16;
+    if (PIX > 128) {  // one workgroup per image, the pixel tiles dealt to its four waves, eight above 20 tiles (k_resstage16_wg)
+        const int tiles = (PIX + 15) / 16;
+        p->family = FAM_RS16_WG; p->imgw = 1; p->waves = tiles > 20 ? 8 : 4; p->nt = (tiles + p->waves - 1) / p->waves;
+        p->lds = ((size_t)(H + 2) * (W + 2) * RS_STRIDE + RS_STRIDE) * sizeof(float); p->block = 64 * p->waves;
+        if (p->lds > dev.lds_per_cu) return PLAN_NO_LDS;
+        p->grid = stage_grid(B, dev, p->lds, 2);
+        return PLAN_OK;
+    }
+    p->family = FAM_RS16;
+    const size_t img_bytes = (size_t)(H + 2) * (W + 2) * RS_STRIDE * sizeof(float);
+    // leaves per wave: as many as fit 8 pixel tiles (accumulators + the kept skip operand in registers) and two workgroups per CU
+    int imgw_max = std::max(1, (16 * 8) / PIX);
+    while (imgw_max > 1 && 4 * (imgw_max * img_bytes + RS_STRIDE * sizeof(float)) + 1024 > 78 * 1024) --imgw_max;
+    const int imgw = pick_leaves_per_wave(B, PIX, imgw_max);
+    return plan_waves(p, B, PIX, imgw, (size_t)16 * ((imgw * PIX + 15) / 16) * sizeof(int) + 4 * (imgw * img_bytes + RS_STRIDE * sizeof(float)), dev, kn.wgs, kn.tail != 0);
+}
+
+static int plan_convpool32(StagePlan *p, long long B, int Cin, int H, int W, const StageDevice &dev, const StageKnobs &kn) {
+    *p = StagePlan{};
+    if (B < 0 || H < 1 || W < 1 || (Cin != 16 && Cin != 32) || H * W > (Cin == 16 ? 640 : 512)) return PLAN_BAD_SHAPE;
+    if (B == 0) return PLAN_OK;
+    const int PIX = H * W;
+    const size_t img_px = (size_t)r32_imgp(H, W);
+    p->cin = Cin;
+    if (PIX > (Cin == 16 ? 112 : 80)) {  // IMGW leaves per workgroup (k_convpool32_wg): at most 40 tiles (Cin 16) / 32 tiles (Cin 32)
+        p->family = FAM_CP_WG;
+        const int rc = plan_wg_group(p, B, PIX, Cin == 16 ? 640 : 512, dev, [&](int k) {
+            return ((std::max<size_t>((k * img_px + 1) * r32_ps(Cin), (size_t)16 * ((k * PIX + 15) / 16) * 36) + 3) & ~(size_t)3) * sizeof(float); });
+        p->wave_floats = (int)(p->lds / sizeof(float));
+        return rc;
+    }
+    p->family = FAM_CP;
+    const int PPn = ((H + 1) / 2) * ((W + 1) / 2);
+    // a wave's region holds its padded images at 36 floats per pixel (x, then the convolution output in place) + the dummy pixel
+    auto wave_floats = [&](int k) { return (size_t)(k * img_px + 1) * CP_PS; };
+    auto lds_bytes = [&](int k) { return ((size_t)16 * ((k * PIX + 15) / 16) + (((size_t)k * PPn + 3) & ~(size_t)3) + 4 * wave_floats(k)) * sizeof(float); };
+    int imgw = (16 * (Cin == 16 ? 7 : 5)) / PIX;  // at most 7 / 5 pixel tiles
+    while (imgw > 1 && lds_bytes(imgw) > 78 * 1024) --imgw;  // two workgroups per CU
+    imgw = pick_leaves_per_wave(B, PIX, imgw);
+    p->wave_floats = (int)wave_floats(imgw);
+    return plan_waves(p, B, PIX, imgw, lds_bytes(imgw), dev, kn.wgs, kn.tail != 0 && Cin == 16);
+}
+
+static int plan_resstage32(StagePlan *p, long long B, int H, int W, const StageDevice &dev, const StageKnobs &kn) {
+    *p = StagePlan{};
+    if (B < 0 || H < 1 || W < 1 || H * W > 512) return PLAN_BAD_SHAPE;
+    if (B == 0) return PLAN_OK;
+    const int PIX = H * W;
+    p->cin = 32;
+    if (PIX > 80) {  // IMGW leaves per workgroup (k_resstage32_wg): the group size with the best fill of 4 waves x nt tiles x 16 rows
+        const size_t img_px = (size_t)r32_imgp(H, W);
+        p->family = FAM_RS32_WG;
+        return plan_wg_group(p, B, PIX, 512, dev, [&](int k) { return (128 + (k * img_px + 1) * r32_ps(32)) * sizeof(float); });  // <= 32 tiles: 8 waves x 4 tiles
+    }
+    if (H == W && (H == 3 || H == 5) && (kn.pm == 1 || (kn.pm != 0 && stage32_pm_cheaper(B, H, W)))) {  // position-major kernels (k_resstage32_pm)
+        const long long tasks = (B + 15) / 16;  // sixteen leaves; at 3x3 one task per wave, at 5x5 one per workgroup (allow_lds checks the fit)
+        p->family = FAM_RS32_PM; p->nt = PIX; p->waves = 4; p->imgw = 16; p->block = 256;
+        p->lds = (128 + (size_t)(H == 3 ? 4 : 1) * PM_IMG_FLOATS(H)) * sizeof(float);
+        p->grid = stage_grid(H == 3 ? (tasks + 3) / 4 : tasks, dev, p->lds, kn.wgs);
+        return PLAN_OK;
+    }
+    p->family = FAM_RS32;
+    int imgw, nt;
+    r32_wave_plan(B, H, W, &imgw, &nt);
+    return plan_waves(p, B, PIX, imgw, r32_wave_lds(H, W, imgw), dev, kn.wgs, false);
+}
+
+// The environment knobs of the stage launchers, entry 0: rp_nn_resstage16, 1: rp_nn_convpool32, 2: rp_nn_resstage32.
+// The workgroup and tail knobs are read once per process, RP_STAGE32_PM at every call: one process can run both kernels.
+static StageKnobs stage_knobs(int entry) {
+    auto env_int = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+    static const int wgs[3] = {env_int("RP_STAGE16_WGS", 2), env_int("RP_CONVPOOL_WGS", 2), env_int("RP_STAGE32_WGS", 2)};  // resident workgroups per CU
+    static const int tail[3] = {env_int("RP_STAGE16_TAIL", 1), env_int("RP_CONVPOOL_TAIL", 1), 0};                           // 0: the tail pixels as a whole tile (A/B)
+    return StageKnobs{wgs[entry], tail[entry], entry == 2 ? env_int("RP_STAGE32_PM", -1) : -1};
+}
+
+// For the host-side tests of the plans, the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
+// out: family, nt, waves, cin, tail, imgw, wave_floats, lds, grid, block (all 0 unless the plan is PLAN_OK).
+extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail,
+                                   int32_t pm_force, int64_t *out) {
+    StagePlan p{};
+    const StageDevice dev{n_cu, (size_t)lds_per_cu};
+    const StageKnobs kn{wgs, tail, pm_force};
+    const int rc = entry == 0 ? plan_resstage16(&p, B, H, W, dev, kn) : entry == 1 ? plan_convpool32(&p, B, Cin, H, W, dev, kn) : plan_resstage32(&p, B, H, W, dev, kn);
+    if (rc != PLAN_OK) p = StagePlan{};
+    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
+    std::copy(f, f + 10, out);
+    return rc;
+}
+extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) {
+    StagePlan p;
+    return plan_resstage32(&p, B, H, W, StageDevice{256, 160 * 1024}, StageKnobs{2, 0, -1}) == PLAN_OK && p.family == FAM_RS32_PM;
+}
+extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
 
 static int grid_for(long long waves) { return (int)((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
@@ -4250,63 +4386,58 @@ extern "C" int rp_nn_resblock16(rp_ctx *ctx, const float *x_dev, const float *fr
     return RP_OK;
 }
 
+// A stage kernel family's instantiations by the plan fields that are its template arguments; the kernels of a table share a signature.
+template <class Fn> struct StageEntry { int nt, waves, cin, tail; Fn fn; };
+typedef void (*StageFn)(const float *, const float *, const float *, float *, float *, long long, int, int, int, const int *);  // ..., B, H, W, IMGW, rows
+typedef void (*StageWg16Fn)(const float *, const float *, const float *, float *, float *, long long, int, int, const int *);  // ..., B, H, W, rows
+typedef void (*StagePmFn)(const float *, const float *, const float *, float *, float *, long long, const int *);              // ..., B, rows
+typedef void (*ConvPoolFn)(const float *, const float *, const float *, float *, long long, int, int, int, int, const int *);  // ..., B, H, W, IMGW, floats, rows
+template <int NT, bool TAIL = false> constexpr StageEntry<StageFn> rs16() { return {NT, 4, 16, TAIL, k_resstage16<NT, TAIL>}; }
+template <int NT, int WV> constexpr StageEntry<StageWg16Fn> rs16_wg() { return {NT, WV, 16, 0, k_resstage16_wg<NT, WV>}; }
+template <int NT> constexpr StageEntry<StageFn> rs32() { return {NT, 4, 32, 0, k_resstage32<NT>}; }
+template <int NT, int WV> constexpr StageEntry<StageFn> rs32_wg() { return {NT, WV, 32, 0, k_resstage32_wg<NT, WV>}; }
+template <int S> constexpr StageEntry<StagePmFn> rs32_pm() { return {S * S, 4, 32, 0, k_resstage32_pm<S>}; }
+template <int NT, int CIN, bool TAIL = false> constexpr StageEntry<ConvPoolFn> cp() { return {NT, 4, CIN, TAIL, k_convpool32<NT, CIN, TAIL>}; }
+template <int NT, int CIN, int WV> constexpr StageEntry<ConvPoolFn> cp_wg() { return {NT, WV, CIN, 0, k_convpool32_wg<NT, CIN, WV>}; }
+static const StageEntry<StageWg16Fn> RS16_WG_TABLE[] = {rs16_wg<3, 4>(), rs16_wg<4, 4>(), rs16_wg<5, 4>(), rs16_wg<3, 8>(), rs16_wg<4, 8>(), rs16_wg<5, 8>()};
+static const StageEntry<StageFn> RS16_TABLE[] = {rs16<6, true>(), rs16<1>(), rs16<2>(), rs16<3>(), rs16<4>(), rs16<5>(), rs16<6>(), rs16<7>(), rs16<8>()};
+static const StageEntry<ConvPoolFn> CP_WG_TABLE[] = {cp_wg<2, 16, 4>(), cp_wg<3, 16, 4>(), cp_wg<4, 16, 4>(), cp_wg<3, 16, 8>(), cp_wg<4, 16, 8>(), cp_wg<5, 16, 8>(),
+                                                     cp_wg<2, 32, 4>(), cp_wg<3, 32, 4>(), cp_wg<4, 32, 4>(), cp_wg<3, 32, 8>(), cp_wg<4, 32, 8>()};
+static const StageEntry<ConvPoolFn> CP_TABLE[] = {cp<6, 16, true>(), cp<1, 16>(), cp<2, 16>(), cp<3, 16>(), cp<4, 16>(), cp<5, 16>(), cp<6, 16>(), cp<7, 16>(),
+                                                  cp<1, 32>(), cp<2, 32>(), cp<3, 32>(), cp<4, 32>(), cp<5, 32>()};
+static const StageEntry<StageFn> RS32_WG_TABLE[] = {rs32_wg<2, 4>(), rs32_wg<3, 4>(), rs32_wg<4, 4>(), rs32_wg<3, 8>(), rs32_wg<4, 8>()};
+static const StageEntry<StagePmFn> RS32_PM_TABLE[] = {rs32_pm<3>(), rs32_pm<5>()};
+static const StageEntry<StageFn> RS32_TABLE[] = {rs32<1>(), rs32<2>(), rs32<3>(), rs32<4>(), rs32<5>()};
+
+// The plan's kernel from its family's table: LDS allowance, launch, launch error.  The arguments convert to the kernel's parameter types.
+template <class... P, size_t N, class... A>
+static int launch_stage(rp_ctx *ctx, const char *what, const StagePlan &p, const StageEntry<void (*)(P...)> (&table)[N], A... args) {
+    for (const auto &e : table) {
+        if (e.nt != p.nt || e.waves != p.waves || e.cin != p.cin || e.tail != p.tail) continue;
+        { const int rc = allow_lds(ctx, (const void *)e.fn, p.lds, what); if (rc != RP_OK) return rc; }
+        hipLaunchKernelGGL(e.fn, dim3(p.grid), dim3(p.block), p.lds, ctx->stream, args...);
+        HIPCHK(ctx, hipGetLastError());
+        return RP_OK;
+    }
+    return fail(ctx, RP_ERR_ARG, "%s: unsupported image size", what);
+}
+// a planner's refusal in the launcher's words
+static int plan_error(rp_ctx *ctx, int rc, const char *what, const char *limits, int H, int W, const StagePlan &p) {
+    if (rc == PLAN_BAD_SHAPE) return fail(ctx, RP_ERR_ARG, "%s: bad argument (%s)", what, limits);
+    if (p.lds == 0) return fail(ctx, RP_ERR_ARG, "%s: a %dx%d image does not fit LDS", what, H, W);
+    return fail(ctx, RP_ERR_ARG, "%s: a %dx%d image needs %zu bytes of LDS%s, the device has %zu per CU", what, H, W, p.lds, p.family == FAM_RS16_WG ? "" : " per workgroup",
+                ctx->lds_per_cu);
+}
+
 extern "C" int rp_nn_resstage16(rp_ctx *ctx, const float *x_dev, const float *frag4_dev, const float *bias4_dev, float *out_dev, float *out_relu_dev, int64_t B,
                                 int32_t H, int32_t W) {
-    if (!ctx || !x_dev || !frag4_dev || !bias4_dev || !out_dev || B < 0 || H < 1 || W < 1 || H * W > 640)
-        return fail(ctx, RP_ERR_ARG, "rp_nn_resstage16: bad argument (images of at most 640 pixels)");
+    const char *what = "rp_nn_resstage16";
+    StagePlan p{};
+    const int rc = !ctx || !x_dev || !frag4_dev || !bias4_dev || !out_dev ? PLAN_BAD_SHAPE : plan_resstage16(&p, B, H, W, StageDevice{ctx->n_cu, ctx->lds_per_cu}, stage_knobs(0));
+    if (rc != PLAN_OK) return plan_error(ctx, rc, what, "images of at most 640 pixels", H, W, p);
     if (B == 0) return RP_OK;
-    const int PIX = H * W;
-    if (PIX > 128) {  // one workgroup per image, the pixel tiles dealt to its four waves (k_resstage16_wg)
-        const int tiles = (PIX + 15) / 16, waves = tiles > 20 ? 8 : 4, nt = (tiles + waves - 1) / waves;
-        const size_t lds = ((size_t)(H + 2) * (W + 2) * RS_STRIDE + RS_STRIDE) * sizeof(float);
-        if (lds > ctx->lds_per_cu) return fail(ctx, RP_ERR_ARG, "rp_nn_resstage16: a %dx%d image needs %zu bytes of LDS, the device has %zu per CU", H, W, lds, ctx->lds_per_cu);
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_per_cu / lds));
-        const dim3 grid((unsigned)std::min<long long>(B, (long long)ctx->n_cu * per_cu)), block(64 * waves);
-#define RSW_LAUNCH(NT_, WV_)                                                                                                                        \
-    case NT_ * 16 + WV_: {                                                                                                                          \
-        const int rc_ = allow_lds(ctx, (const void *)k_resstage16_wg<NT_, WV_>, lds, "rp_nn_resstage16"); if (rc_ != RP_OK) return rc_;            \
-        hipLaunchKernelGGL((k_resstage16_wg<NT_, WV_>), grid, block, lds, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, (int)H, (int)W, ctx->nn_rows_dev); \
-    } break;
-        switch (nt * 16 + waves) {
-            RSW_LAUNCH(3, 4) RSW_LAUNCH(4, 4) RSW_LAUNCH(5, 4) RSW_LAUNCH(3, 8) RSW_LAUNCH(4, 8) RSW_LAUNCH(5, 8)
-            default: return fail(ctx, RP_ERR_ARG, "rp_nn_resstage16: unsupported image size");
-        }
-#undef RSW_LAUNCH
-        HIPCHK(ctx, hipGetLastError());
-        return RP_OK;
-    }
-    const size_t img_bytes = (size_t)(H + 2) * (W + 2) * RS_STRIDE * sizeof(float);
-    // leaves per wave: as many as fit 8 pixel tiles (accumulators + the kept skip operand in registers) and two workgroups per CU
-    int imgw_max = std::max(1, (16 * 8) / PIX);
-    while (imgw_max > 1 && 4 * (imgw_max * img_bytes + RS_STRIDE * sizeof(float)) + 1024 > 78 * 1024) --imgw_max;
-    const int imgw = pick_leaves_per_wave(B, PIX, imgw_max);
-    const int nt = (imgw * PIX + 15) / 16;
-    const size_t lds = (size_t)16 * nt * sizeof(int) + 4 * (imgw * img_bytes + RS_STRIDE * sizeof(float));
-    const long long tasks = (B + imgw - 1) / imgw;
-    static const int stage_wgs = getenv("RP_STAGE16_WGS") ? atoi(getenv("RP_STAGE16_WGS")) : 2;  // resident workgroups per CU (registers: 2 waves per SIMD)
-    if (lds > ctx->lds_per_cu) return fail(ctx, RP_ERR_ARG, "rp_nn_resstage16: a %dx%d image needs %zu bytes of LDS per workgroup, the device has %zu per CU", H, W, lds, ctx->lds_per_cu);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)stage_wgs, ctx->lds_per_cu / lds));
-    const dim3 grid((unsigned)std::min<long long>((tasks + 3) / 4, (long long)ctx->n_cu * per_cu)), block(256);
-#define RS_LAUNCH(NT_)                                                                                                                              \
-    case NT_:                                                                                                                                       \
-        { const int rc_ = allow_lds(ctx, (const void *)k_resstage16<NT_>, lds, "rp_nn_resstage16"); if (rc_ != RP_OK) return rc_; }                \
-        hipLaunchKernelGGL((k_resstage16<NT_>), grid, block, lds, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, (int)H, (int)W, imgw, ctx->nn_rows_dev); \
-        break;
-    static const int rs16_tail = getenv("RP_STAGE16_TAIL") ? atoi(getenv("RP_STAGE16_TAIL")) : 1;  // 0: the tail pixels as a whole tile (A/B)
-    const int tail_px = (imgw * PIX) & 15;
-    if (rs16_tail && nt == 7 && tail_px >= 1 && tail_px <= 4) {  // six tiles + a tail of up to four pixels (10x10: 96 + 4)
-        { const int rc_ = allow_lds(ctx, (const void *)k_resstage16<6, true>, lds, "rp_nn_resstage16"); if (rc_ != RP_OK) return rc_; }
-        hipLaunchKernelGGL((k_resstage16<6, true>), grid, block, lds, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, (int)H, (int)W, imgw, ctx->nn_rows_dev);
-        HIPCHK(ctx, hipGetLastError());
-        return RP_OK;
-    }
-    switch (nt) {
-        RS_LAUNCH(1) RS_LAUNCH(2) RS_LAUNCH(3) RS_LAUNCH(4) RS_LAUNCH(5) RS_LAUNCH(6) RS_LAUNCH(7) RS_LAUNCH(8)
-        default: return fail(ctx, RP_ERR_ARG, "rp_nn_resstage16: unsupported image size");
-    }
-#undef RS_LAUNCH
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    if (p.family == FAM_RS16_WG) return launch_stage(ctx, what, p, RS16_WG_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, ctx->nn_rows_dev);
+    return launch_stage(ctx, what, p, RS16_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, p.imgw, ctx->nn_rows_dev);
 }
 
 extern "C" int rp_nn_pack_conv32(rp_ctx *ctx, const float *w_dev, float *frag_dev, int32_t Cin) {
@@ -4319,159 +4450,25 @@ extern "C" int rp_nn_pack_conv32(rp_ctx *ctx, const float *w_dev, float *frag_de
 
 extern "C" int rp_nn_convpool32(rp_ctx *ctx, const float *x_dev, const float *frag_dev, const float *bias_dev, float *out_dev, int64_t B, int32_t Cin, int32_t H,
                                 int32_t W) {
-    if (!ctx || !x_dev || !frag_dev || !bias_dev || !out_dev || B < 0 || H < 1 || W < 1 || (Cin != 16 && Cin != 32) || H * W > (Cin == 16 ? 640 : 512))
-        return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: bad argument (Cin 16: <= 640 pixels, Cin 32: <= 512 pixels)");
+    const char *what = "rp_nn_convpool32";
+    StagePlan p{};
+    const int rc = !ctx || !x_dev || !frag_dev || !bias_dev || !out_dev ? PLAN_BAD_SHAPE : plan_convpool32(&p, B, Cin, H, W, StageDevice{ctx->n_cu, ctx->lds_per_cu}, stage_knobs(1));
+    if (rc != PLAN_OK) return plan_error(ctx, rc, what, "Cin 16: <= 640 pixels, Cin 32: <= 512 pixels", H, W, p);
     if (B == 0) return RP_OK;
-    if (H * W > (Cin == 16 ? 112 : 80)) {  // IMGW leaves per workgroup (k_convpool32_wg)
-        const int PIXw = H * W, max_nt = Cin == 16 ? 10 : 8;  // tile rows per workgroup in units of 64: 40 tiles (Cin 16) / 32 tiles (Cin 32)
-        const size_t img_px = (size_t)r32_imgp(H, W);
-        auto floats_of = [&](int k) { return (std::max<size_t>((k * img_px + 1) * r32_ps(Cin), (size_t)16 * ((k * PIXw + 15) / 16) * 36) + 3) & ~(size_t)3; };
-        int imgw = 0, nt = 0, waves = 4;
-        long long best = -1;
-        for (int k = 1; k * PIXw <= 64 * max_nt && floats_of(k) * sizeof(float) <= ctx->lds_per_cu; ++k) {
-            const int tk = (k * PIXw + 15) / 16, wk = tk > 16 ? 8 : 4, ntk = (tk + wk - 1) / wk;
-            const long long cost = wg_group_cost(B, k, wk * ntk, ctx->n_cu);
-            if (best < 0 || cost < best) { best = cost; imgw = k; nt = ntk; waves = wk; }
-        }
-        if (imgw == 0) return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: a %dx%d image does not fit LDS", H, W);
-        const size_t wf = floats_of(imgw), lds = wf * sizeof(float);
-        const long long tasks = (B + imgw - 1) / imgw;
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_per_cu / lds));
-        const dim3 grid((unsigned)std::min<long long>(tasks, (long long)ctx->n_cu * per_cu)), block(64 * waves);
-#define CPW_LAUNCH(NT_, CIN_, WV_)                                                                                                                   \
-    case (NT_ * 64 + CIN_) * 16 + WV_: {                                                                                                             \
-        const int rc_ = allow_lds(ctx, (const void *)k_convpool32_wg<NT_, CIN_, WV_>, lds, "rp_nn_convpool32"); if (rc_ != RP_OK) return rc_;        \
-        hipLaunchKernelGGL((k_convpool32_wg<NT_, CIN_, WV_>), grid, block, lds, ctx->stream, x_dev, frag_dev, bias_dev, out_dev, (long long)B,       \
-                           (int)H, (int)W, imgw, (int)wf, ctx->nn_rows_dev);                                                                         \
-    } break;
-        switch ((nt * 64 + (int)Cin) * 16 + waves) {
-            CPW_LAUNCH(2, 16, 4) CPW_LAUNCH(3, 16, 4) CPW_LAUNCH(4, 16, 4) CPW_LAUNCH(3, 16, 8) CPW_LAUNCH(4, 16, 8) CPW_LAUNCH(5, 16, 8)
-            CPW_LAUNCH(2, 32, 4) CPW_LAUNCH(3, 32, 4) CPW_LAUNCH(4, 32, 4) CPW_LAUNCH(3, 32, 8) CPW_LAUNCH(4, 32, 8)
-            default: return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: unsupported image size");
-        }
-#undef CPW_LAUNCH
-        HIPCHK(ctx, hipGetLastError());
-        return RP_OK;
-    }
-    const int PIX = H * W, max_tiles = Cin == 16 ? 7 : 5;
-    const size_t img_pixels = (size_t)r32_imgp(H, W);
-    int imgw = (16 * max_tiles) / PIX;
-    const int PPn = ((H + 1) / 2) * ((W + 1) / 2);
-    // a wave's region holds its padded images at 36 floats per pixel (x, then the convolution output in place) + the dummy pixel
-    auto wave_floats = [&](int k) { return (size_t)(k * img_pixels + 1) * CP_PS; };
-    auto lds_bytes = [&](int k) { return ((size_t)16 * ((k * PIX + 15) / 16) + (((size_t)k * PPn + 3) & ~(size_t)3) + 4 * wave_floats(k)) * sizeof(float); };
-    while (imgw > 1 && lds_bytes(imgw) > 78 * 1024) --imgw;  // two workgroups per CU
-    imgw = pick_leaves_per_wave(B, PIX, imgw);
-    const int nt = (imgw * PIX + 15) / 16;
-    const size_t wf = wave_floats(imgw), lds = lds_bytes(imgw);
-    if (lds > ctx->lds_per_cu) return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: a %dx%d image needs %zu bytes of LDS per workgroup, the device has %zu per CU", H, W, lds, ctx->lds_per_cu);
-    const long long tasks = (B + imgw - 1) / imgw;
-    static const int cp_wgs = getenv("RP_CONVPOOL_WGS") ? atoi(getenv("RP_CONVPOOL_WGS")) : 2;  // resident workgroups per CU (experiments)
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)cp_wgs, ctx->lds_per_cu / lds));
-    const dim3 grid((unsigned)std::min<long long>((tasks + 3) / 4, (long long)ctx->n_cu * per_cu)), block(256);  // persistent waves
-#define CP_LAUNCH(NT_, CIN_)                                                                                                                         \
-    {                                                                                                                                                \
-        const int rc_ = allow_lds(ctx, (const void *)k_convpool32<NT_, CIN_>, lds, "rp_nn_convpool32"); if (rc_ != RP_OK) return rc_;                \
-        hipLaunchKernelGGL((k_convpool32<NT_, CIN_>), grid, block, lds, ctx->stream, x_dev, frag_dev, bias_dev, out_dev, (long long)B, (int)H,        \
-                           (int)W, imgw, (int)wf, ctx->nn_rows_dev);                                                                                 \
-    }
-    static const int cp_tail = getenv("RP_CONVPOOL_TAIL") ? atoi(getenv("RP_CONVPOOL_TAIL")) : 1;  // 0: the tail pixels as a whole tile (A/B)
-    const int tail_px = (imgw * PIX) & 15;
-    if (cp_tail && Cin == 16 && nt == 7 && tail_px >= 1 && tail_px <= 4) {  // six tiles + a tail of up to four pixels (10x10: 96 + 4)
-        const int rc_ = allow_lds(ctx, (const void *)k_convpool32<6, 16, true>, lds, "rp_nn_convpool32"); if (rc_ != RP_OK) return rc_;
-        hipLaunchKernelGGL((k_convpool32<6, 16, true>), grid, block, lds, ctx->stream, x_dev, frag_dev, bias_dev, out_dev, (long long)B, (int)H, (int)W, imgw, (int)wf, ctx->nn_rows_dev);
-    } else if (Cin == 16) {
-        switch (nt) {
-            case 1: CP_LAUNCH(1, 16) break; case 2: CP_LAUNCH(2, 16) break; case 3: CP_LAUNCH(3, 16) break; case 4: CP_LAUNCH(4, 16) break;
-            case 5: CP_LAUNCH(5, 16) break; case 6: CP_LAUNCH(6, 16) break; case 7: CP_LAUNCH(7, 16) break;
-            default: return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: unsupported image size");
-        }
-    } else {
-        switch (nt) {
-            case 1: CP_LAUNCH(1, 32) break; case 2: CP_LAUNCH(2, 32) break; case 3: CP_LAUNCH(3, 32) break; case 4: CP_LAUNCH(4, 32) break;
-            case 5: CP_LAUNCH(5, 32) break;
-            default: return fail(ctx, RP_ERR_ARG, "rp_nn_convpool32: unsupported image size");
-        }
-    }
-#undef CP_LAUNCH
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    if (p.family == FAM_CP_WG) return launch_stage(ctx, what, p, CP_WG_TABLE, x_dev, frag_dev, bias_dev, out_dev, B, H, W, p.imgw, p.wave_floats, ctx->nn_rows_dev);
+    return launch_stage(ctx, what, p, CP_TABLE, x_dev, frag_dev, bias_dev, out_dev, B, H, W, p.imgw, p.wave_floats, ctx->nn_rows_dev);
 }
 
 extern "C" int rp_nn_resstage32(rp_ctx *ctx, const float *x_dev, const float *frag4_dev, const float *bias4_dev, float *out_dev, float *out_relu_dev, int64_t B,
                                 int32_t H, int32_t W) {
-    if (!ctx || !x_dev || !frag4_dev || !bias4_dev || !out_dev || B < 0 || H < 1 || W < 1 || H * W > 512)
-        return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: bad argument (images of at most 512 pixels)");
+    const char *what = "rp_nn_resstage32";
+    StagePlan p{};
+    const int rc = !ctx || !x_dev || !frag4_dev || !bias4_dev || !out_dev ? PLAN_BAD_SHAPE : plan_resstage32(&p, B, H, W, StageDevice{ctx->n_cu, ctx->lds_per_cu}, stage_knobs(2));
+    if (rc != PLAN_OK) return plan_error(ctx, rc, what, "images of at most 512 pixels", H, W, p);
     if (B == 0) return RP_OK;
-    const int PIX = H * W;
-    if (PIX > 80) {  // IMGW leaves per workgroup (k_resstage32_wg): the group size with the best fill of 4 waves x nt tiles x 16 rows
-        const size_t img_px = (size_t)r32_imgp(H, W);
-        auto lds_of = [&](int k) { return (128 + (k * img_px + 1) * r32_ps(32)) * sizeof(float); };
-        int imgw = 1, nt = 0, waves = 4;
-        long long best = -1;
-        for (int k = 1; k * PIX <= 512 && lds_of(k) <= ctx->lds_per_cu; ++k) {  // <= 32 tiles: 8 waves x 4 tiles
-            const int tk = (k * PIX + 15) / 16, wk = tk > 16 ? 8 : 4, ntk = (tk + wk - 1) / wk;
-            const long long cost = wg_group_cost(B, k, wk * ntk, ctx->n_cu);
-            if (best < 0 || cost < best) { best = cost; imgw = k; nt = ntk; waves = wk; }
-        }
-        if (nt == 0) return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: a %dx%d image does not fit LDS", H, W);
-        const size_t lds = lds_of(imgw);
-        const long long tasks = (B + imgw - 1) / imgw;
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_per_cu / lds));
-        const dim3 grid((unsigned)std::min<long long>(tasks, (long long)ctx->n_cu * per_cu)), block(64 * waves);
-#define RSW_LAUNCH(NT_, WV_)                                                                                                                        \
-    case NT_ * 16 + WV_: {                                                                                                                          \
-        const int rc_ = allow_lds(ctx, (const void *)k_resstage32_wg<NT_, WV_>, lds, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_;            \
-        hipLaunchKernelGGL((k_resstage32_wg<NT_, WV_>), grid, block, lds, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, (int)H, (int)W, imgw, ctx->nn_rows_dev); \
-    } break;
-        switch (nt * 16 + waves) {
-            RSW_LAUNCH(2, 4) RSW_LAUNCH(3, 4) RSW_LAUNCH(4, 4) RSW_LAUNCH(3, 8) RSW_LAUNCH(4, 8)
-            default: return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: unsupported image size");
-        }
-#undef RSW_LAUNCH
-        HIPCHK(ctx, hipGetLastError());
-        return RP_OK;
-    }
-    int imgw, nt;
-    r32_wave_plan(B, H, W, &imgw, &nt);
-    static const int rs32_wgs = getenv("RP_STAGE32_WGS") ? atoi(getenv("RP_STAGE32_WGS")) : 2;  // resident workgroups per CU (experiments)
-    if (H == W && (H == 3 || H == 5)) {  // position-major kernels (k_resstage32_pm)
-        const char *pm_env = getenv("RP_STAGE32_PM");  // 0: never, 1: always (read at every call: one process can run both)
-        const int pm_force = pm_env ? atoi(pm_env) : -1;
-        if (pm_force == 1 || (pm_force != 0 && stage32_pm_cheaper(B, H, W))) {
-            const size_t lds_pm = (128 + (size_t)(H == 3 ? 4 : 1) * PM_IMG_FLOATS(H)) * sizeof(float);
-            const long long tasks_pm = (B + 15) / 16, wgs = H == 3 ? (tasks_pm + 3) / 4 : tasks_pm;
-            const int per_cu_pm = (int)std::max<size_t>(1, std::min<size_t>((size_t)rs32_wgs, ctx->lds_per_cu / lds_pm));
-            const dim3 grid_pm((unsigned)std::min<long long>(wgs, (long long)ctx->n_cu * per_cu_pm)), block_pm(256);  // persistent
-            if (H == 3) {
-                const int rc_ = allow_lds(ctx, (const void *)k_resstage32_pm<3>, lds_pm, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_;
-                hipLaunchKernelGGL(k_resstage32_pm<3>, grid_pm, block_pm, lds_pm, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, ctx->nn_rows_dev);
-            } else {
-                const int rc_ = allow_lds(ctx, (const void *)k_resstage32_pm<5>, lds_pm, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_;
-                hipLaunchKernelGGL(k_resstage32_pm<5>, grid_pm, block_pm, lds_pm, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, (long long)B, ctx->nn_rows_dev);
-            }
-            HIPCHK(ctx, hipGetLastError());
-            return RP_OK;
-        }
-    }
-    const size_t lds = r32_wave_lds(H, W, imgw);
-    if (lds > ctx->lds_per_cu) return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: a %dx%d image needs %zu bytes of LDS per workgroup, the device has %zu per CU", H, W, lds, ctx->lds_per_cu);
-    const long long tasks = (B + imgw - 1) / imgw;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)rs32_wgs, ctx->lds_per_cu / lds));
-    const dim3 grid((unsigned)std::min<long long>((tasks + 3) / 4, (long long)ctx->n_cu * per_cu)), block(256);  // persistent waves
-#define RS_LAUNCH(NT_)                                                                                                                              \
-    case NT_:                                                                                                                                       \
-        { const int rc_ = allow_lds(ctx, (const void *)k_resstage32<NT_>, lds, "rp_nn_resstage32"); if (rc_ != RP_OK) return rc_; }                \
-        hipLaunchKernelGGL(k_resstage32<NT_>, grid, block, lds, ctx->stream, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev,                    \
-                           (long long)B, (int)H, (int)W, imgw, ctx->nn_rows_dev);                                                                   \
-        break;
-    switch (nt) {
-        RS_LAUNCH(1) RS_LAUNCH(2) RS_LAUNCH(3) RS_LAUNCH(4) RS_LAUNCH(5)
-        default: return fail(ctx, RP_ERR_ARG, "rp_nn_resstage32: unsupported image size");
-    }
-#undef RS_LAUNCH
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    if (p.family == FAM_RS32_PM) return launch_stage(ctx, what, p, RS32_PM_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, ctx->nn_rows_dev);
+    if (p.family == FAM_RS32_WG) return launch_stage(ctx, what, p, RS32_WG_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, p.imgw, ctx->nn_rows_dev);
+    return launch_stage(ctx, what, p, RS32_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, p.imgw, ctx->nn_rows_dev);
 }
 
 extern "C" int rp_leaf_states(rp_ctx *ctx, int32_t max_rows, uint64_t *rows_out, uint8_t *remaining_out, int32_t *slot_out, int32_t *n_out) {

@@ -7,6 +7,7 @@ import pytest
 
 import evaluators as ev
 import oracle_lib as orc
+import stage_shapes
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -525,7 +526,7 @@ def test_fused_resblock16_kernel_matches_pytorch_block():
 
 def test_fused_resstage16_kernel_matches_pytorch_blocks():
     """rp_nn_resstage16 (both residual blocks of the 16-channel stage: four 3x3 convolutions in place on one LDS image) against
-    the module's two blocks through PyTorch, for every tile count the kernel is instantiated for."""
+    the module's two blocks through PyTorch, for every tile count the kernels are instantiated for (test_stage_plans_host.py checks that)."""
     import torch
     from resource_packing_self_play_amd import _lib
     d = np.load(os.path.join(GOLDEN, "nnet_c3_seed0.npz"))
@@ -535,11 +536,7 @@ def test_fused_resstage16_kernel_matches_pytorch_blocks():
     st = net.nnet.conv_seqs[0]
     net.refresh_fused(); keep = net.nnet.refresh_frags(eng)
     frag4, bias4 = net.nnet._dense["stagefrag:0"], net.nnet._dense["stagebias:0"]
-    # images above 128 pixels run one workgroup per image (k_resstage16_wg: 4 or 8 waves share the tiles): 25x25 is the 50x50 board's
-    # 10x10 (96 + 4 pixels), 9x11 (96 + 3) and 7x14 (96 + 2) take their last pixels through the 4x4x1 tail blocks
-    # (8000 leaves of 5x5: four leaves per wave = 96 + 4 pixels: a tail tile across images)
-    for (B, H, W) in [(5, 10, 10), (1030, 10, 10), (6, 9, 11), (5, 7, 14), (8000, 5, 5), (64, 7, 9), (33, 3, 3), (17, 8, 8), (9, 5, 5), (3, 1, 1), (21, 11, 11), (6, 8, 16), (7, 5, 13),
-                      (5, 25, 25), (530, 25, 25), (3, 20, 32), (4, 12, 12), (2, 16, 20), (3, 9, 33), (2, 21, 17)]:
+    for (B, H, W) in stage_shapes.RESSTAGE16:
         x = torch.randn(B, 16, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
         with torch.no_grad():
             want = st.res_block1(st.res_block0(x))
@@ -578,9 +575,7 @@ def test_fused_resstage32_kernel_matches_pytorch_blocks():
     for si in (1, 2):
         st = net.nnet.conv_seqs[si]
         frag4, bias4 = net.nnet._dense["stagefrag:%d" % si], net.nnet._dense["stagebias:%d" % si]
-        # above 80 pixels: several leaves per WORKGROUP (k_resstage32_wg); 13x13 is the 50x50 board's second stage
-        for (B, H, W) in [(5, 5, 5), (1030, 5, 5), (3001, 3, 3), (7, 3, 3), (64, 4, 4), (33, 2, 3), (3, 1, 1), (10, 8, 8), (11, 7, 9), (4, 8, 10), (13, 6, 6),
-                          (7, 13, 13), (1000, 13, 13), (5, 10, 10), (3, 16, 16), (2, 22, 23), (4, 9, 11), (5, 12, 20)]:
+        for (B, H, W) in stage_shapes.RESSTAGE32:
             x = torch.randn(B, 32, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
             with torch.no_grad():
                 want = st.res_block1(st.res_block0(x))
@@ -614,12 +609,7 @@ def test_fused_convpool32_kernel_matches_pytorch_conv_and_pool():
     from resource_packing_self_play_amd import _lib
     eng = _lib.Engine(20, 20, 32, 1, 1, stream=torch.cuda.current_stream().cuda_stream)
     torch.manual_seed(6)
-    cases = [(16, 5, 10, 10), (16, 1030, 10, 10), (16, 6, 9, 11), (16, 5, 7, 14), (16, 8000, 5, 5), (16, 33, 7, 9),  # 10x10 / 9x11 / 7x14: 96 pixels + a 4x4x1 tail of 4 / 3 / 2 (16, 9, 3, 3), (16, 4, 1, 1), (16, 21, 8, 13), (16, 64, 4, 4),
-             (32, 5, 5, 5), (32, 1030, 5, 5), (32, 3001, 3, 3), (32, 17, 8, 8), (32, 11, 7, 9), (32, 6, 2, 5), (32, 3, 1, 1), (32, 10, 8, 10),
-             # above 112 / 80 pixels: k_convpool32_wg (25x25x16 -> 13x13x32 and 13x13x32 -> 7x7x32 at the 50x50 board)
-             (16, 5, 25, 25), (16, 300, 25, 25), (16, 3, 12, 12), (16, 4, 20, 31), (16, 2, 9, 33), (32, 7, 13, 13), (32, 500, 13, 13), (32, 4, 16, 16),
-             (32, 3, 22, 23), (32, 5, 10, 10), (32, 2, 9, 11)]
-    for (cin, B, H, W) in cases:
+    for (cin, B, H, W) in stage_shapes.CONVPOOL32:
         conv = torch.nn.Conv2d(cin, 32, 3, padding=1).cuda()
         frag = torch.empty(9 * cin * 32, device="cuda")
         eng.nn_pack_conv32(conv.weight.detach().contiguous(), frag)

@@ -7,12 +7,11 @@ import os
 import numpy as np
 import pytest
 
+from stage_shapes import STAGE32_PM_BATCHES as BATCHES
 from test_gpu_nnet import GOLDEN, gpu_wrapper
 
 pytestmark = pytest.mark.gpu
 
-# short last task, exactly one task, one leaf into the next task, more tasks than one round of a small grid
-BATCHES = {3: (1, 15, 16, 17, 33, 1030), 5: (1, 15, 16, 17, 65, 1030)}
 CASES = [(S, si, B) for S in (3, 5) for si in (1, 2) for B in BATCHES[S]]
 
 

@@ -10,6 +10,7 @@ LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 
 @pytest.fixture(scope="module")
 def lib():
+    import torch  # noqa: F401  (its HIP runtime first: a later _lib.load() in this process refuses two of them)
     L = ctypes.CDLL(LIB)
     L.rp_debug_stage32_pm_pick.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     L.rp_debug_stage32_pm_swz.argtypes = [ctypes.c_int32]
