@@ -3124,6 +3124,141 @@ __global__ void __launch_bounds__(256, 2) k_resstage32_pm(const float *__restric
     }
 }
 
+// Position-major entry of a 32-channel stage on 5x5 images: the 3x3 convolution 32 -> 32 + bias + max_pool2d(3, 2, 1) -> 3x3 that
+// k_convpool32<5, 32> below computes pixel-major (three leaves per wave, 75 of 80 columns, all nine taps: 240 tile-taps per leaf).  Same
+// image, wave roles and instruction streams as k_resstage32_pm<5> (PmTab<5, ROLE>: 169 tile-taps per leaf), ONE convolution per task:
+// x goes into the image WITHOUT ReLU (a stage's first convolution takes x as it is), conv + bias is written in place over the wave's
+// own positions, and the pooled 3x3 image is read back from there -- output (pr, px) is the max over the rows 2 pr - 1 .. 2 pr + 1 and
+// columns 2 px - 1 .. 2 px + 1 inside the image (4 / 6 / 9 positions, 49 reads), the nine outputs dealt to the four waves by window
+// size.  The sums run in r32_conv_t's order from the same fragments and the maximum is exact, so the result is k_convpool32's bits
+// (up to the sign of a zero).  The next task's x is requested before the MFMA stream and stored after the pooling barrier.
+__host__ __device__ constexpr int cp_pm_out(int role, int i) {  // i-th pooled output (pr * 3 + px) of a wave role, -1 past its last
+    constexpr int t[4][3] = {{4, 0, -1}, {1, 3, -1}, {5, 7, -1}, {2, 6, 8}};  // centre + corner / edges / edges / corners: 13 / 12 / 12 / 12 reads
+    return i < 3 ? t[role][i] : -1;
+}
+__host__ __device__ constexpr int cp_pm_win(int pp, int i) {  // i-th (0..8) cell of output pp's window: the conv position, -1 outside the 5x5 image
+    const int r = 2 * (pp / 3) - 1 + i / 3, c = 2 * (pp % 3) - 1 + i % 3;
+    return (r >= 0 && r < 5 && c >= 0 && c < 5) ? r * 5 + c : -1;
+}
+constexpr int cp_pm_reads(int role) {
+    int n = 0;
+    for (int o = 0; o < 3 && cp_pm_out(role, o) >= 0; ++o)
+        for (int i = 0; i < 9; ++i) n += cp_pm_win(cp_pm_out(role, o), i) >= 0;
+    return n;
+}
+constexpr bool cp_pm_covers() {  // every pooled output dealt once, every conv position read at least once
+    int outs[9] = {}, seen[25] = {};
+    for (int role = 0; role < 4; ++role)
+        for (int o = 0; o < 3 && cp_pm_out(role, o) >= 0; ++o) {
+            ++outs[cp_pm_out(role, o)];
+            for (int i = 0; i < 9; ++i)
+                if (cp_pm_win(cp_pm_out(role, o), i) >= 0) ++seen[cp_pm_win(cp_pm_out(role, o), i)];
+        }
+    for (int i = 0; i < 9; ++i) if (outs[i] != 1) return false;
+    for (int i = 0; i < 25; ++i) if (seen[i] < 1) return false;
+    return true;
+}
+static_assert(cp_pm_reads(0) + cp_pm_reads(1) + cp_pm_reads(2) + cp_pm_reads(3) == 49 && cp_pm_covers(), "5x5 -> 3x3 pooling: nine windows, 49 reads");
+#define CP_PM_LDS_BYTES (PM_IMG_FLOATS(5) * sizeof(float))  // the image alone: the bias quads stay in registers
+template <int ROLE>
+__device__ __forceinline__ void cp_pm_body(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias, float *__restrict__ out,
+                                           long long B, long long leaf0, long long stride_leaves, float *img) {
+    using T = PmTab<5, ROLE>;
+    constexpr int NP = T::L.np, NE = T::L.n, PIX = 25, PP = 9, CONV_BYTES = 9 * 32 * 32 * 4;
+    const int lane = lane_id(), n = lane & 15, g = lane >> 4, sw = pm_swz(n);
+    const float *rb0 = img + n * 32 + 4 * ((2 * g) ^ sw), *rb1 = img + n * 32 + 4 * ((2 * g + 1) ^ sw);
+    float *wb0 = img + n * 32 + 4 * (g ^ sw), *wb1 = img + n * 32 + 4 * ((4 + g) ^ sw);
+    const int voff = lane * 16, xoff = n * (PIX * 128) + g * 16, ooff = n * (PP * 128) + g * 16;  // byte offsets: weight piece; (leaf n, quad g) of x / out
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)frag, 0, CONV_BYTES, RS_BUF_FLAGS);
+    const f32x4 ba = *(const f32x4 *)(bias + 4 * g), bb = *(const f32x4 *)(bias + 16 + 4 * g);
+    f32x4 xs[NP][2], acc[NP][2], wq[3][2], bq[3];
+    auto load_x = [&](long long l0) {  // leaves past B: the loads return zeros
+        const int nb = (int)(B - l0 < 16 ? B - l0 : 16) * PIX * 128;
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)l0 * PIX * 32), 0, nb, RS_BUF_FLAGS);
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value, p = T::L.pos[k];
+            xs[k][0] = rs_load_x(xrs, xoff, p * 128); xs[k][1] = rs_load_x(xrs, xoff, p * 128 + 64);
+        });
+    };
+    auto b_read = [&](auto E) {
+        constexpr int e = decltype(E)::value, off = T::L.q[e] * 512;
+        return *(const f32x4 *)(((T::L.s[e] & 1) ? rb1 : rb0) + off);
+    };
+    load_x(leaf0);
+    wq[0][0] = rs_load_b(frs, voff, 0); wq[0][1] = rs_load_b(frs, voff, 1024);
+    wq[1][0] = rs_load_b(frs, voff, 2048); wq[1][1] = rs_load_b(frs, voff, 3072);
+    for (; leaf0 < B; leaf0 += stride_leaves) {
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value, p = T::L.pos[k];
+            *(f32x4 *)(wb0 + p * 512) = xs[k][0]; *(f32x4 *)(wb1 + p * 512) = xs[k][1];
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        if (leaf0 + stride_leaves < B) load_x(leaf0 + stride_leaves);  // uniform: the four waves loop over the same tasks
+        lds_barrier();
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            acc[k][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[k][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        });
+        bq[0] = b_read(std::integral_constant<int, 0>{}); bq[1] = b_read(std::integral_constant<int, 1>{});
+        pm_for<NE>([&](auto E) {
+            constexpr int e = decltype(E)::value, s = T::L.s[e], k = T::L.k[e];
+            if constexpr (e == 0 || T::L.s[e > 0 ? e - 1 : 0] != s) {  // first entry of half-tap s: the fragments of half-tap s + 2 (the next task reads the same convolution)
+                constexpr int s2 = s + 2, off = (s2 < 18 ? s2 : s2 - 18) * 2048;
+                wq[s2 % 3][0] = rs_load_b(frs, voff, off); wq[s2 % 3][1] = rs_load_b(frs, voff, off + 1024);
+            }
+            if constexpr (e + 2 < NE) bq[(e + 2) % 3] = b_read(std::integral_constant<int, (e + 2 < NE ? e + 2 : 0)>{});
+            const f32x4 w0 = wq[s % 3][0], w1 = wq[s % 3][1], b = bq[e % 3];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[k][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[j], b[j], acc[k][0], 0, 0, 0);
+                acc[k][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[j], b[j], acc[k][1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        lds_barrier();  // every wave has read the image: conv + bias may overwrite it
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value, p = T::L.pos[k];
+            *(f32x4 *)(wb0 + p * 512) = acc[k][0] + ba; *(f32x4 *)(wb1 + p * 512) = acc[k][1] + bb;
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        lds_barrier();
+        const int obytes = (int)(B - leaf0 < 16 ? B - leaf0 : 16) * PP * 128;  // leaves past B: the stores are dropped
+        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)leaf0 * PP * 32), 0, obytes, RS_BUF_FLAGS);
+        pm_for<3>([&](auto O) {  // this wave's pooled outputs: the lane's leaf, channel quads g and 4 + g
+            constexpr int pp = cp_pm_out(ROLE, decltype(O)::value);
+            if constexpr (pp >= 0) {
+                f32x4 m0 = *(const f32x4 *)(wb0 + cp_pm_win(pp, 4) * 512), m1 = *(const f32x4 *)(wb1 + cp_pm_win(pp, 4) * 512);  // the centre lies inside
+                pm_for<9>([&](auto I) {
+                    constexpr int q = cp_pm_win(pp, decltype(I)::value);
+                    if constexpr (q >= 0 && decltype(I)::value != 4) {
+                        const f32x4 v0 = *(const f32x4 *)(wb0 + q * 512), v1 = *(const f32x4 *)(wb1 + q * 512);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { m0[j] = fmaxf(m0[j], v0[j]); m1[j] = fmaxf(m1[j], v1[j]); }
+                    }
+                });
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m0), ors, ooff, pp * 128, RS_STREAM_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m1), ors, ooff, pp * 128 + 64, RS_STREAM_AUX);
+            }
+        });
+        lds_barrier();  // the windows have been read: the next task's x may overwrite the image
+    }
+}
+__global__ void __launch_bounds__(256, 2) k_convpool32_pm(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
+                                                          float *__restrict__ out, long long B, const int *__restrict__ nrows_dev) {
+    extern __shared__ __attribute__((aligned(16))) float rb_lds[];
+    const int wv = wave_in_block();
+    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    if ((long long)blockIdx.x * 16 >= B) return;
+    const long long leaf0 = (long long)blockIdx.x * 16, stride = (long long)gridDim.x * 16;  // the same tasks for the four waves: uniform barriers
+    switch (wv) {
+        case 0: cp_pm_body<0>(x, frag, bias, out, B, leaf0, stride, rb_lds); break;
+        case 1: cp_pm_body<1>(x, frag, bias, out, B, leaf0, stride, rb_lds); break;
+        case 2: cp_pm_body<2>(x, frag, bias, out, B, leaf0, stride, rb_lds); break;
+        default: cp_pm_body<3>(x, frag, bias, out, B, leaf0, stride, rb_lds); break;
+    }
+}
+
 // Entry of a 32-channel stage (ConvSequence.conv + max_pool2d(3, 2, 1), BinpackingNNet.py:34,39-40): 3x3 convolution
 // CIN -> 32 channels over the pixels of IMGW consecutive leaves (same transposed MFMA stream as above), bias, then the 3x3 / stride-2
 // max-pool.  Round 3: the padded images have a pixel stride of 36 floats for either CIN, and the convolution output + bias (32
@@ -3654,6 +3789,14 @@ static bool stage32_pm_cheaper(long long B, int H, int W) {
     return cost_pm < cost_old;
 }
 
+// k_convpool32 or k_convpool32_pm for the 32 -> 32 entry on 5x5 images, by the same measure: imgw leaves in nt tiles x 9 taps per wave and
+// round against 43 (position, tap) pairs of the busiest wave role over STAGE_WAVES / 4 workgroups.
+static bool convpool32_pm_cheaper(long long B, int imgw) {
+    if (B <= 0) return false;
+    const int nt = (imgw * 25 + 15) / 16;
+    return pm_rounds_cost(B, 16, STAGE_WAVES / 4) * 43 < pm_rounds_cost(B, imgw, STAGE_WAVES) * nt * 9;
+}
+
 // Leaves per WORKGROUP for the _wg stage kernels.  A CU works through its workgroups' pixel tiles at a fixed rate, so a launch takes
 // (workgroups on the busiest CU) x (tile slots of a workgroup = waves x tiles per wave): few large groups fill their tiles best but
 // quantise badly over the CUs (1 024 leaves in groups of 3 = 342 workgroups = 2 rounds on 86 CUs, 1 on the rest).  Cost for all B rows
@@ -3667,11 +3810,12 @@ static long long wg_group_cost(long long B, int k, int tile_slots, int n_cu) {
 // What one stage launch looks like, from the shape, the device figures and the knobs alone (no rp_ctx, no environment, no HIP call):
 // the kernel family and its template arguments (nt tiles per wave, waves, input channels, tail blocks; k_resstage32_pm: nt = the S * S
 // pixel positions), the leaves per wave or workgroup, the wave_floats argument of the convpool kernels, LDS bytes, grid and block.
-enum { FAM_NONE, FAM_RS16, FAM_RS16_WG, FAM_RS32, FAM_RS32_WG, FAM_RS32_PM, FAM_CP, FAM_CP_WG };
+enum { FAM_NONE, FAM_RS16, FAM_RS16_WG, FAM_RS32, FAM_RS32_WG, FAM_RS32_PM, FAM_CP, FAM_CP_WG, FAM_CP_PM };
 enum { PLAN_OK, PLAN_BAD_SHAPE, PLAN_NO_LDS };
 struct StagePlan { int family, nt, waves, cin, tail, imgw, wave_floats; size_t lds; unsigned grid, block; };
 struct StageDevice { int n_cu; size_t lds_per_cu; };
-struct StageKnobs { int wgs, tail, pm; };  // resident workgroups per CU; tail blocks on / off; position-major 0: never, 1: always, -1: where cheaper
+// resident workgroups per CU; tail blocks on / off; position-major stage (pm) and 5x5 entry (cp_pm) kernels 0: never, 1: always, -1: where cheaper
+struct StageKnobs { int wgs, tail, pm, cp_pm; };
 
 // persistent grid: the work items, at most the workgroups that are resident at once (wgs per CU, fewer where LDS holds fewer)
 static unsigned stage_grid(long long work, const StageDevice &dev, size_t lds, int wgs) {
@@ -3747,6 +3891,13 @@ static int plan_convpool32(StagePlan *p, long long B, int Cin, int H, int W, con
     int imgw = (16 * (Cin == 16 ? 7 : 5)) / PIX;  // at most 7 / 5 pixel tiles
     while (imgw > 1 && lds_bytes(imgw) > 78 * 1024) --imgw;  // two workgroups per CU
     imgw = pick_leaves_per_wave(B, PIX, imgw);
+    // position-major entry kernel (k_convpool32_pm) for 32 channels on 5x5; a device whose LDS cannot hold its image keeps k_convpool32
+    if (Cin == 32 && H == 5 && W == 5 && CP_PM_LDS_BYTES <= dev.lds_per_cu && (kn.cp_pm == 1 || (kn.cp_pm != 0 && convpool32_pm_cheaper(B, imgw)))) {
+        p->family = FAM_CP_PM; p->nt = PIX; p->waves = 4; p->imgw = 16; p->block = 256;
+        p->lds = CP_PM_LDS_BYTES;
+        p->grid = stage_grid((B + 15) / 16, dev, p->lds, kn.wgs);
+        return PLAN_OK;
+    }
     p->wave_floats = (int)wave_floats(imgw);
     return plan_waves(p, B, PIX, imgw, lds_bytes(imgw), dev, kn.wgs, kn.tail != 0 && Cin == 16);
 }
@@ -3776,12 +3927,12 @@ static int plan_resstage32(StagePlan *p, long long B, int H, int W, const StageD
 }
 
 // The environment knobs of the stage launchers, entry 0: rp_nn_resstage16, 1: rp_nn_convpool32, 2: rp_nn_resstage32.
-// The workgroup and tail knobs are read once per process, RP_STAGE32_PM at every call: one process can run both kernels.
+// The workgroup and tail knobs are read once per process, RP_STAGE32_PM and RP_CONVPOOL_PM at every call: one process can run both kernels.
 static StageKnobs stage_knobs(int entry) {
     auto env_int = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
     static const int wgs[3] = {env_int("RP_STAGE16_WGS", 2), env_int("RP_CONVPOOL_WGS", 2), env_int("RP_STAGE32_WGS", 2)};  // resident workgroups per CU
     static const int tail[3] = {env_int("RP_STAGE16_TAIL", 1), env_int("RP_CONVPOOL_TAIL", 1), 0};                           // 0: the tail pixels as a whole tile (A/B)
-    return StageKnobs{wgs[entry], tail[entry], entry == 2 ? env_int("RP_STAGE32_PM", -1) : -1};
+    return StageKnobs{wgs[entry], tail[entry], entry == 2 ? env_int("RP_STAGE32_PM", -1) : -1, entry == 1 ? env_int("RP_CONVPOOL_PM", -1) : 0};
 }
 
 // For the host-side tests of the plans, the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
@@ -3790,8 +3941,17 @@ extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_
                                    int32_t pm_force, int64_t *out) {
     StagePlan p{};
     const StageDevice dev{n_cu, (size_t)lds_per_cu};
-    const StageKnobs kn{wgs, tail, pm_force};
+    const StageKnobs kn{wgs, tail, pm_force, 0};  // the recorded plans (tests/golden/stage_plans.json) are k_convpool32's: rp_debug_convpool_plan has the knob
     const int rc = entry == 0 ? plan_resstage16(&p, B, H, W, dev, kn) : entry == 1 ? plan_convpool32(&p, B, Cin, H, W, dev, kn) : plan_resstage32(&p, B, H, W, dev, kn);
+    if (rc != PLAN_OK) p = StagePlan{};
+    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
+    std::copy(f, f + 10, out);
+    return rc;
+}
+extern "C" int rp_debug_convpool_plan(int32_t Cin, int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail, int32_t cp_pm,
+                                      int64_t *out) {  // rp_debug_stage_plan's entry 1 with the RP_CONVPOOL_PM knob
+    StagePlan p{};
+    const int rc = plan_convpool32(&p, B, Cin, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, cp_pm});
     if (rc != PLAN_OK) p = StagePlan{};
     const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
     std::copy(f, f + 10, out);
@@ -3799,7 +3959,7 @@ extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_
 }
 extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) {
     StagePlan p;
-    return plan_resstage32(&p, B, H, W, StageDevice{256, 160 * 1024}, StageKnobs{2, 0, -1}) == PLAN_OK && p.family == FAM_RS32_PM;
+    return plan_resstage32(&p, B, H, W, StageDevice{256, 160 * 1024}, StageKnobs{2, 0, -1, 0}) == PLAN_OK && p.family == FAM_RS32_PM;
 }
 extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
 
@@ -4391,6 +4551,7 @@ template <class Fn> struct StageEntry { int nt, waves, cin, tail; Fn fn; };
 typedef void (*StageFn)(const float *, const float *, const float *, float *, float *, long long, int, int, int, const int *);  // ..., B, H, W, IMGW, rows
 typedef void (*StageWg16Fn)(const float *, const float *, const float *, float *, float *, long long, int, int, const int *);  // ..., B, H, W, rows
 typedef void (*StagePmFn)(const float *, const float *, const float *, float *, float *, long long, const int *);              // ..., B, rows
+typedef void (*ConvPoolPmFn)(const float *, const float *, const float *, float *, long long, const int *);                     // ..., B, rows
 typedef void (*ConvPoolFn)(const float *, const float *, const float *, float *, long long, int, int, int, int, const int *);  // ..., B, H, W, IMGW, floats, rows
 template <int NT, bool TAIL = false> constexpr StageEntry<StageFn> rs16() { return {NT, 4, 16, TAIL, k_resstage16<NT, TAIL>}; }
 template <int NT, int WV> constexpr StageEntry<StageWg16Fn> rs16_wg() { return {NT, WV, 16, 0, k_resstage16_wg<NT, WV>}; }
@@ -4405,6 +4566,7 @@ static const StageEntry<ConvPoolFn> CP_WG_TABLE[] = {cp_wg<2, 16, 4>(), cp_wg<3,
                                                      cp_wg<2, 32, 4>(), cp_wg<3, 32, 4>(), cp_wg<4, 32, 4>(), cp_wg<3, 32, 8>(), cp_wg<4, 32, 8>()};
 static const StageEntry<ConvPoolFn> CP_TABLE[] = {cp<6, 16, true>(), cp<1, 16>(), cp<2, 16>(), cp<3, 16>(), cp<4, 16>(), cp<5, 16>(), cp<6, 16>(), cp<7, 16>(),
                                                   cp<1, 32>(), cp<2, 32>(), cp<3, 32>(), cp<4, 32>(), cp<5, 32>()};
+static const StageEntry<ConvPoolPmFn> CP_PM_TABLE[] = {{25, 4, 32, 0, k_convpool32_pm}};
 static const StageEntry<StageFn> RS32_WG_TABLE[] = {rs32_wg<2, 4>(), rs32_wg<3, 4>(), rs32_wg<4, 4>(), rs32_wg<3, 8>(), rs32_wg<4, 8>()};
 static const StageEntry<StagePmFn> RS32_PM_TABLE[] = {rs32_pm<3>(), rs32_pm<5>()};
 static const StageEntry<StageFn> RS32_TABLE[] = {rs32<1>(), rs32<2>(), rs32<3>(), rs32<4>(), rs32<5>()};
@@ -4455,6 +4617,7 @@ extern "C" int rp_nn_convpool32(rp_ctx *ctx, const float *x_dev, const float *fr
     const int rc = !ctx || !x_dev || !frag_dev || !bias_dev || !out_dev ? PLAN_BAD_SHAPE : plan_convpool32(&p, B, Cin, H, W, StageDevice{ctx->n_cu, ctx->lds_per_cu}, stage_knobs(1));
     if (rc != PLAN_OK) return plan_error(ctx, rc, what, "Cin 16: <= 640 pixels, Cin 32: <= 512 pixels", H, W, p);
     if (B == 0) return RP_OK;
+    if (p.family == FAM_CP_PM) return launch_stage(ctx, what, p, CP_PM_TABLE, x_dev, frag_dev, bias_dev, out_dev, B, ctx->nn_rows_dev);
     if (p.family == FAM_CP_WG) return launch_stage(ctx, what, p, CP_WG_TABLE, x_dev, frag_dev, bias_dev, out_dev, B, H, W, p.imgw, p.wave_floats, ctx->nn_rows_dev);
     return launch_stage(ctx, what, p, CP_TABLE, x_dev, frag_dev, bias_dev, out_dev, B, H, W, p.imgw, p.wave_floats, ctx->nn_rows_dev);
 }

@@ -25,7 +25,9 @@ def means(src, counter):
                 name = r.get("Kernel_Name", "")
                 for k in KERNELS:
                     if k in name:
-                        if k in ("k_resstage32", "k_convpool32"):  # two instantiations per wave: keep them apart by template arguments
+                        if "k_convpool32_pm" in name:  # no template arguments; "<pm>" keeps it apart and among bench.py's k_convpool32 candidates
+                            k = "k_convpool32<pm>"
+                        elif k in ("k_resstage32", "k_convpool32"):  # two instantiations per wave: keep them apart by template arguments
                             k = k + name[name.index("<"):name.index(">") + 1] if "<" in name else k
                         a = acc.setdefault(k, [0, 0.0])
                         a[0] += 1; a[1] += float(r.get("Counter_Value", 0) or 0)
