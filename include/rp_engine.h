@@ -33,8 +33,9 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 5  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
-                             5: placement trace (rp_set_trace, rp_pop_finished_packings) */
+#define RP_ABI_VERSION 6  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+                             5: placement trace (rp_set_trace, rp_pop_finished_packings)
+                             6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -257,8 +258,15 @@ int rp_leaf_states(rp_ctx *ctx, int32_t max_rows, uint64_t *rows_out /*[n][H]*/,
 int rp_commit_eval(rp_ctx *ctx, const float *pi_dev, const float *v_dev);
 /* The same from the policy head's raw outputs (logits_fc, BinpackingNNet.py:69,79): the softmax of NNet.predict (NNet.py:81-85:
  * exp(log_softmax(x))) is taken inside the kernel, float32, exp(x - max) / sum -- no separate softmax pass over [n][W*N].
- * W * N <= 1536 (the row lives in LDS); larger action spaces take the softmax first and call rp_commit_eval. */
+ * W * N <= 1536 (a lane keeps its 24 elements of the row in registers); larger action spaces are refused with RP_ERR_ARG and go
+ * through rp_commit_eval_logits_wide, or take the softmax first and call rp_commit_eval. */
 int rp_commit_eval_logits(rp_ctx *ctx, const float *logits_dev, const float *v_dev);
+/* The same contract for every geometry the engine accepts (W * N <= 8192): the wave stages the row in LDS and makes its passes there,
+ * one wave per workgroup (rp_debug_commit_plan).  The arithmetic, float32, in this order: m = max of the row; e[a] = expf(x[a] - m);
+ * lane l adds the e of a = l, l + 64, l + 128, ... in ascending order, the 64 lane sums are combined by the xor butterfly with
+ * offsets 32, 16, ... 1; p[a] = e[a] / sum, one division per element.  rp_commit_eval_logits computes exactly that, so where both
+ * apply (W * N <= 1536) the two calls leave bit-identical trees. */
+int rp_commit_eval_logits_wide(rp_ctx *ctx, const float *logits_dev, const float *v_dev);
 /* Same with HOST float32 buffers (tests, CPU evaluators). */
 int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const float *v_host, int32_t n_rows);
 
@@ -343,6 +351,11 @@ int rp_dump_tree(rp_ctx *ctx, int32_t slot, uint64_t *node_rows, uint8_t *node_r
                  uint8_t *node_term_kind, uint8_t *node_expanded, uint32_t *node_ns, uint32_t *node_edge_off,
                  uint32_t *node_n_valid, uint16_t *edge_action, double *edge_p, double *edge_q, uint32_t *edge_nsa,
                  uint8_t *edge_q_kind, uint32_t *edge_child);
+/* Launch plan of rp_commit_eval_logits_wide for A actions, n_leaves blocks of the pairwise sum over A and G slots on a device with
+ * lds_per_cu bytes of LDS per CU -- host arithmetic only, no context and no device.  out[8]: waves per workgroup, LDS bytes per
+ * workgroup, grid, block, then one wave's parts in bytes: row, block sums, terms, mask.  0: fits; 1: bad argument; 2: the
+ * workgroup's LDS exceeds lds_per_cu (out is filled in). */
+int rp_debug_commit_plan(int32_t A, int32_t n_leaves, int64_t G, int64_t lds_per_cu, int64_t *out);
 /* Device self-tests used by the GPU parity suite: sqrt / Q-update / NumPy-order sum on device,
  * host buffers in and out. */
 int rp_selftest_sqrt(rp_ctx *ctx, int64_t n, double *sqrt_n_out, double *sqrt_n_eps_out);

@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -80,6 +80,7 @@ _SIGS = {
     "rp_leaf_states": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "rp_commit_eval": (C.c_int, [_vp, _vp, _vp]),
     "rp_commit_eval_logits": (C.c_int, [_vp, _vp, _vp]),
+    "rp_commit_eval_logits_wide": (C.c_int, [_vp, _vp, _vp]),
     "rp_commit_eval_host": (C.c_int, [_vp, _vp, _vp, _i32]),
     "rp_root_counts": (C.c_int, [_vp, _i32, _i32, _vp]),
     "rp_game_status": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -99,6 +100,7 @@ _SIGS = {
     "rp_tree_size": (C.c_int, [_vp, _i32, _vp, _vp]),
     "rp_arena_peak": (C.c_int, [_vp, _vp, _vp, _vp]),
     "rp_dump_tree": (C.c_int, [_vp, _i32] + [_vp] * 14),
+    "rp_debug_commit_plan": (C.c_int, [_i32, _i32, _i64, _i64, _vp]),
     "rp_selftest_sqrt": (C.c_int, [_vp, _i64, _vp, _vp]),
     "rp_selftest_q_update": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_selftest_masked_prior": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
@@ -454,10 +456,15 @@ class Engine:
     def commit_eval(self, pi_dev_ptr, v_dev_ptr):
         self._ck(self.L.rp_commit_eval(self.h, C.c_void_p(pi_dev_ptr), C.c_void_p(v_dev_ptr)))
 
-    LOGITS_MAX_ACTIONS = 1536  # rp_commit_eval_logits keeps a row in LDS
+    LOGITS_MAX_ACTIONS = 1536  # rp_commit_eval_logits keeps a row in registers, 24 elements per lane
+    WIDE_LOGITS_MAX_ACTIONS = 8192  # rp_commit_eval_logits_wide keeps it in LDS: every action space of the ABI
 
     def commit_eval_logits(self, logits_dev_ptr, v_dev_ptr):
         self._ck(self.L.rp_commit_eval_logits(self.h, C.c_void_p(logits_dev_ptr), C.c_void_p(v_dev_ptr)))
+
+    def commit_eval_logits_wide(self, logits_dev_ptr, v_dev_ptr):
+        """The same softmax, bit for bit, with the row staged in LDS: any action space."""
+        self._ck(self.L.rp_commit_eval_logits_wide(self.h, C.c_void_p(logits_dev_ptr), C.c_void_p(v_dev_ptr)))
 
     def commit_eval_host(self, pi, v):
         pi = _arr(pi, np.float32); n = pi.shape[0]

@@ -582,15 +582,21 @@ template <typename row_t, bool BIG = true> struct Tree {
         arena_reset(va, p.N + 1, p.peak_chunks + (size_t)g * 2 + 1);
     }
     // a node's header as wave-uniform scalars (one 32-byte vector load, eight readfirstlanes)
-    __device__ __forceinline__ NodeHdr load_hdr(u32 node) const {
+    // fetch_hdr only requests the two loads, so a caller can put other memory traffic between the request and decode_hdr's use of it
+    struct RawHdr { uint4 a, b; };
+    __device__ __forceinline__ RawHdr fetch_hdr(u32 node) const {
         static_assert(sizeof(NodeHdr) == 32, "NodeHdr is eight dwords");
         const uint4 *q = (const uint4 *)(hdr + node);
-        const uint4 a = q[0], b = q[1];
+        return RawHdr{q[0], q[1]};
+    }
+    static __device__ __forceinline__ NodeHdr decode_hdr(const RawHdr &r) {
+        const uint4 a = r.a, b = r.b;
         u32 w[8] = {uni(a.x), uni(a.y), uni(a.z), uni(a.w), uni(b.x), uni(b.y), uni(b.z), uni(b.w)};
         NodeHdr h;
         __builtin_memcpy(&h, w, sizeof h);
         return h;
     }
+    __device__ __forceinline__ NodeHdr load_hdr(u32 node) const { return decode_hdr(fetch_hdr(node)); }
     static __device__ __forceinline__ int level_of(int N, u64 rem0, u64 rem1) { return N - __popcll(rem0) - __popcll(rem1); }
 
     // key of a node -> lane-resident rows + uniform remaining words.  The key is H rows followed by the remaining-item words, so ONE
@@ -1389,24 +1395,79 @@ __device__ double masked_prior(const DP &p, const float *pi, const u16 *act, flo
 }
 
 // Expansion + backup for the waiting leaves (MCTS_bpp.py:87-104 then :130-139 up the path).
-// LOGITS: `pi` holds the policy head's raw outputs (logits_fc, BinpackingNNet.py:69,79) and the softmax of NNet.predict
-// (exp(log_softmax(x)), NNet.py:81-85) is taken here -- the row goes to LDS once, max / exp / sum / divide run in the wave, and the
-// masked NumPy-order sum below reads the probabilities from LDS: the separate softmax pass over the [rows][A] matrix (one read + one
-// write of 84 MB per wave of 32 768 leaves at 20x20 / 32) and the re-read by this kernel are gone.  float32 like torch.softmax:
-// exp(x - max) / sum, the sum taken lane-wise then across lanes (the policy tolerance is 1e-5, not bit equality with one library).
-template <typename row_t, bool LOGITS>
+// MODE 0 (COMMIT_PROBS): `pi` holds probabilities.
+// MODE 1 (COMMIT_LOGITS_REG) and 2 (COMMIT_LOGITS_LDS): `pi` holds the policy head's raw outputs (logits_fc, BinpackingNNet.py:69,79) and
+// the softmax of NNet.predict (exp(log_softmax(x)), NNet.py:81-85) is taken here -- the row goes to LDS once, max / exp / sum / divide run
+// in the wave, and the masked NumPy-order sum below reads the probabilities from LDS: the separate softmax pass over the [rows][A] matrix
+// (one read + one write of 84 MB per wave of 32 768 leaves at 20x20 / 32) and the re-read by this kernel are gone.  float32 like
+// torch.softmax (the policy tolerance is 1e-5, not bit equality with one library), in ONE order for both modes: lane l owns the
+// elements a = l + 64 i; m = the row's maximum; e[a] = expf(x[a] - m); every lane adds its e in ascending i, the 64 lane sums meet in the
+// xor butterfly o = 32 ... 1; p[a] = e[a] / sum.  Mode 1 keeps the lane's elements in 24 registers (A <= 1536, four waves per workgroup);
+// mode 2 stages the row in the wave's LDS buffer and makes the passes there (any A <= 8192, one wave per workgroup: plan_commit_lds),
+// so the two give the same bits wherever mode 1 applies.
+enum { COMMIT_PROBS = 0, COMMIT_LOGITS_REG = 1, COMMIT_LOGITS_LDS = 2 };
+// the per-element arithmetic of the softmax, shared by the two logits modes
+__device__ __forceinline__ float softmax_exp(float x, float m) { return expf(x - m); }
+__device__ __forceinline__ float softmax_div(float e, float sum) { return e / sum; }
+__device__ __forceinline__ float wave_max(float m) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    return m;
+}
+__device__ __forceinline__ float wave_sum(float sum) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+    return sum;
+}
+// Pass 1 of mode 2: the wave copies the A logits at `row` into its LDS buffer `sp` and returns the lane's running maximum (the maximum
+// is exact, so which lane saw which element does not matter).  16-byte loads and LDS stores where the row allows them: `sp` is 16-byte
+// aligned by the layout, the global row when A is a multiple of 4 and the matrix itself is aligned.
+__device__ __forceinline__ float stage_logits_row(const float *row, float *sp, int A, int lane) {
+    float m = -INFINITY;
+    if ((A & 3) == 0 && (((size_t)row) & 15) == 0) {
+        const float4 *r4 = (const float4 *)row;
+        float4 *s4 = (float4 *)sp;
+        const int n4 = A >> 2;
+#pragma unroll 8
+        for (int i = lane; i < n4; i += 64) {
+            const float4 x = r4[i];
+            s4[i] = x;
+            m = fmaxf(fmaxf(m, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
+        }
+    } else {
+#pragma unroll 8
+        for (int a = lane; a < A; a += 64) {
+            const float x = row[a];
+            sp[a] = x;
+            m = fmaxf(m, x);
+        }
+    }
+    return m;
+}
+template <typename row_t, int MODE>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_commit(DP p, const float *pi, const float *vv) {
-    // LDS per wave, all of it sized by the action space (commit_lds_bytes): n_leaves float64 block sums, min(A, TERM_CHUNK) float32
-    // terms, (LOGITS) A float32 probabilities, ceil(A / 32) mask words -- 5.3 KB per wave at A = 640, so the workgroups per CU are
+    // LDS per wave, all of it sized by the action space (commit_wave_lds): n_leaves float64 block sums, min(A, TERM_CHUNK) float32
+    // terms, (logits) A float32 probabilities, ceil(A / 32) mask words -- 5.3 KB per wave at A = 640, so the workgroups per CU are
     // bounded by registers (7 waves per SIMD), not by LDS (round 2 / 3: 9.7 KB per wave with float64 terms and worst-case tables: 4)
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    const int g = blockIdx.x * WAVES_PER_BLOCK + wave_in_block(), lane = lane_id(), wv = wave_in_block();
+    constexpr int WPB = MODE == COMMIT_LOGITS_LDS ? 1 : WAVES_PER_BLOCK;  // waves per workgroup (mode 2: plan_commit_lds)
+    const int wv = WPB == 1 ? 0 : wave_in_block(), g = blockIdx.x * WPB + wv, lane = lane_id();
     if (g >= p.G) return;
     const int tchunk = p.A < TERM_CHUNK ? p.A : TERM_CHUNK, mwords = ((p.A + 31) >> 5) + 1;
-    double *s_leaf_w = s_dyn + (size_t)wv * p.n_leaves;
-    float *s_term_w = (float *)(s_dyn + (size_t)WAVES_PER_BLOCK * p.n_leaves) + (size_t)wv * tchunk;
-    float *s_soft = (float *)(s_dyn + (size_t)WAVES_PER_BLOCK * p.n_leaves) + (size_t)WAVES_PER_BLOCK * tchunk;
-    u32 *s_mask_w = (u32 *)(s_soft + (LOGITS ? (size_t)WAVES_PER_BLOCK * p.A : 0)) + (size_t)wv * mwords;
+    double *s_leaf_w;
+    float *s_term_w, *s_soft;
+    u32 *s_mask_w;
+    if (MODE == COMMIT_LOGITS_LDS) {  // the row first (16-byte aligned: A rounded up to 4 floats), then as below
+        s_soft = (float *)s_dyn;
+        s_leaf_w = (double *)(s_soft + ((p.A + 3) & ~3));
+        s_term_w = (float *)(s_leaf_w + p.n_leaves);
+        s_mask_w = (u32 *)(s_term_w + tchunk);
+    } else {
+        s_leaf_w = s_dyn + (size_t)wv * p.n_leaves;
+        s_term_w = (float *)(s_dyn + (size_t)WAVES_PER_BLOCK * p.n_leaves) + (size_t)wv * tchunk;
+        s_soft = (float *)(s_dyn + (size_t)WAVES_PER_BLOCK * p.n_leaves) + (size_t)WAVES_PER_BLOCK * tchunk;
+        s_mask_w = (u32 *)(s_soft + (MODE == COMMIT_LOGITS_REG ? (size_t)WAVES_PER_BLOCK * p.A : 0)) + (size_t)wv * mwords;
+    }
     // One wave per SLOT: the slot's phase, leaf, path and evaluator row are requested together (one memory round trip) -- a wave per
     // evaluator ROW first had to fetch the row's slot (eval_slot[b]) and only then the slot's state.  Slots that wait for nothing leave.
     const int phase = p.phase[g];
@@ -1421,31 +1482,48 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_commit(DP p, const flo
     const double v = (double)vv[b];  // float32 array of shape (1,) (NNet.py:85)
     const float *row = pi + (size_t)b * p.A;
     constexpr int LPL = 24;  // logits per lane: A <= 1536 (rp_commit_eval_logits checks)
-    float xr[LOGITS ? LPL : 1];
-    if (LOGITS) {  // the row's logits are requested with the slot's state and stay in registers (-inf past the row: exp gives 0)
+    float xr[MODE == COMMIT_LOGITS_REG ? LPL : 1];
+    if (MODE == COMMIT_LOGITS_REG) {  // the row's logits are requested with the slot's state and stay in registers (-inf past the row: exp gives 0)
 #pragma unroll
         for (int i = 0; i < LPL; ++i) { const int a = lane + 64 * i; xr[i] = (64 * i < p.A && a < p.A) ? row[a] : -INFINITY; }
     }
     Tree<row_t> t(p, g);
-    NodeHdr hd = t.load_hdr(uni(node));
+    NodeHdr hd;
+    float m = -INFINITY;
+    if (MODE == COMMIT_LOGITS_LDS) {  // pass 1: the row streams into LDS while the header's request is in flight
+        const typename Tree<row_t>::RawHdr raw = t.fetch_hdr(uni(node));
+        m = stage_logits_row(row, s_soft, p.A, lane);
+        hd = Tree<row_t>::decode_hdr(raw);
+    } else {
+        hd = t.load_hdr(uni(node));
+    }
     // backup along the stored path (:130-139) first: its loads travel with the header's
     if (lane < depth) t.backup_entry(n0, e0, v, RP_KIND_F32);
     if (lane + 64 < depth) t.backup_entry(n1, e1, v, RP_KIND_F32);
-    if (LOGITS) {
+    if (MODE == COMMIT_LOGITS_REG) {
         float *sp = s_soft + (size_t)wv * p.A;
-        float m = xr[0];
+        m = xr[0];
 #pragma unroll
         for (int i = 1; i < LPL; ++i) m = fmaxf(m, xr[i]);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = wave_max(m);
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < LPL; ++i)
-            if (64 * i < p.A) { xr[i] = expf(xr[i] - m); sum += xr[i]; }  // uniform: whole 64-wide groups past the row are skipped
+            if (64 * i < p.A) { xr[i] = softmax_exp(xr[i], m); sum += xr[i]; }  // uniform: whole 64-wide groups past the row are skipped
+        sum = wave_sum(sum);
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-#pragma unroll
-        for (int i = 0; i < LPL; ++i) { const int a = lane + 64 * i; if (64 * i < p.A && a < p.A) sp[a] = xr[i] / sum; }
+        for (int i = 0; i < LPL; ++i) { const int a = lane + 64 * i; if (64 * i < p.A && a < p.A) sp[a] = softmax_div(xr[i], sum); }
+        wave_sync();
+        row = sp;
+    }
+    if (MODE == COMMIT_LOGITS_LDS) {
+        float *sp = s_soft;
+        m = wave_max(m);
+        lds_sync();  // pass 1 placed the elements by its own lane mapping; from here lane l owns a = l + 64 i
+        float sum = 0.f;
+        for (int a = lane; a < p.A; a += 64) { const float e = softmax_exp(sp[a], m); sp[a] = e; sum += e; }  // pass 2
+        sum = wave_sum(sum);
+        for (int a = lane; a < p.A; a += 64) sp[a] = softmax_div(sp[a], sum);  // pass 3
         wave_sync();
         row = sp;
     }
@@ -3963,6 +4041,44 @@ extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) {
 }
 extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
 
+// LDS of one wave of k_commit: n_leaves float64 block sums, min(A, TERM_CHUNK) float32 terms, ceil(A / 32) + 1 mask words and, for the
+// logits modes, the row's `row_floats` probabilities.
+struct CommitWaveLds { size_t row, leaf, term, mask; size_t total() const { return row + leaf + term + mask; } };
+static CommitWaveLds commit_wave_lds(int A, int n_leaves, size_t row_floats) {
+    return CommitWaveLds{row_floats * sizeof(float), (size_t)n_leaves * sizeof(double), (size_t)std::min(A, TERM_CHUNK) * sizeof(float),
+                         (size_t)(((A + 31) >> 5) + 1) * sizeof(u32)};
+}
+// Launch shape of k_commit's LDS-row mode (COMMIT_LOGITS_LDS) for G slots -- pure host code, no device needed (rp_debug_commit_plan).
+// The kernel has no workgroup barrier and its waves share nothing, so the workgroup shape only decides how LDS is handed out: a
+// workgroup of w waves takes w rows at once and holds them until its last wave is done.  One wave per workgroup keeps
+// floor(LDS / per-wave bytes) waves resident, which no larger workgroup can beat (w floor(LDS / (w x)) <= floor(LDS / x): 15 waves
+// against 12 with four-wave workgroups at A = 1 600, 5 against 4 at A = 6 400), frees a row the moment its wave ends, and stays under
+// 39 KB at A = 8 192 -- below the 64 KB above which a kernel needs hipFuncSetAttribute.  Single-wave workgroups are not counted against
+// the CU's workgroup slots, and at the G these action spaces run with (768 at 50x50 / 128) the grid is a few waves per CU either way.
+struct CommitPlan { int waves, grid, block; CommitWaveLds part; size_t lds; };
+enum { COMMIT_PLAN_OK = 0, COMMIT_PLAN_ARG = 1, COMMIT_PLAN_LDS = 2 };
+static int plan_commit_lds(CommitPlan *out, int A, int n_leaves, long long G, size_t lds_per_cu) {
+    if (A < 1 || A > 8192 || n_leaves < 1 || n_leaves > MAX_LEAVES || G < 1 || G > 0x7FFFFFFFLL) return COMMIT_PLAN_ARG;
+    CommitPlan p{};
+    p.waves = 1;
+    p.part = commit_wave_lds(A, n_leaves, (size_t)((A + 3) & ~3));  // the row starts the buffer and is padded to 16 bytes
+    p.lds = (size_t)p.waves * p.part.total();
+    p.grid = (int)((G + p.waves - 1) / p.waves);
+    p.block = 64 * p.waves;
+    *out = p;
+    return p.lds <= lds_per_cu ? COMMIT_PLAN_OK : COMMIT_PLAN_LDS;
+}
+// out: waves per workgroup, LDS bytes per workgroup, grid, block, then the per-wave parts: row, block sums, terms, mask (bytes).
+extern "C" int rp_debug_commit_plan(int32_t A, int32_t n_leaves, int64_t G, int64_t lds_per_cu, int64_t *out) {
+    CommitPlan p{};
+    const int rc = out && lds_per_cu >= 0 ? plan_commit_lds(&p, A, n_leaves, G, (size_t)lds_per_cu) : COMMIT_PLAN_ARG;
+    if (!out) return rc;
+    const int64_t f[8] = {p.waves, (int64_t)p.lds, p.grid, p.block, (int64_t)p.part.row, (int64_t)p.part.leaf, (int64_t)p.part.term, (int64_t)p.part.mask};
+    std::copy(f, f + 8, out);
+    return rc;
+}
+static const void *commit_lds_kernel(const rp_ctx *ctx) { return ctx->row64 ? (const void *)k_commit<u64, COMMIT_LOGITS_LDS> : (const void *)k_commit<u32, COMMIT_LOGITS_LDS>; }
+
 static int grid_for(long long waves) { return (int)((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
 // Dynamic LDS above the default 64 KB limit has to be allowed per kernel; a size the device cannot give is an argument error with
@@ -4163,6 +4279,17 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
                 delete ctx;
                 return fail(nullptr, rc2, "%s", msg.c_str());
             }
+        }
+    }
+    if (d.A > 1536) {  // the LDS-row commit (rp_commit_eval_logits_wide) is these contexts' production route and first runs inside a graph capture
+        CommitPlan pl{};
+        int rc2 = plan_commit_lds(&pl, d.A, d.n_leaves, d.G, ctx->lds_per_cu) == COMMIT_PLAN_ARG ? fail(ctx, RP_ERR_ARG, "rp_create: no launch plan for the LDS-row commit") : RP_OK;
+        if (rc2 == RP_OK) rc2 = allow_lds(ctx, commit_lds_kernel(ctx), pl.lds, "rp_create (LDS row of the commit kernel)");
+        if (rc2 != RP_OK) {
+            const std::string msg = ctx->err;
+            for (void *p : ctx->allocs) (void)hipFree(p);
+            delete ctx;
+            return fail(nullptr, rc2, "%s", msg.c_str());
         }
     }
     *out = ctx;
@@ -4656,17 +4783,27 @@ extern "C" int rp_leaf_states(rp_ctx *ctx, int32_t max_rows, uint64_t *rows_out,
     return RP_OK;
 }
 
-static int launch_commit(rp_ctx *ctx, const float *pi_dev, const float *v_dev, bool logits) {
+static int launch_commit(rp_ctx *ctx, const float *pi_dev, const float *v_dev, int mode) {
     const DP &d = ctx->d;
-    const dim3 grid(grid_for(d.G)), block(64 * WAVES_PER_BLOCK);  // one wave per slot; waiting slots find their evaluator row in game_row
-    const size_t lds = (size_t)WAVES_PER_BLOCK * ((size_t)d.n_leaves * sizeof(double) + (size_t)std::min(d.A, TERM_CHUNK) * sizeof(float) +
-                                                 (logits ? (size_t)d.A * sizeof(float) : 0) + (size_t)(((d.A + 31) >> 5) + 1) * sizeof(u32));
-    if (logits) {
-        if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, true>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-        else hipLaunchKernelGGL((k_commit<u32, true>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+    if (mode == COMMIT_LOGITS_LDS) {
+        CommitPlan pl;
+        const int rc = plan_commit_lds(&pl, d.A, d.n_leaves, d.G, ctx->lds_per_cu);
+        if (rc == COMMIT_PLAN_ARG) return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits_wide: no launch plan for %d actions, %d slots", d.A, d.G);
+        // no hipFuncSetAttribute here: the launch may sit inside a graph capture, and rp_create has allowed what A > 1536 asks for
+        if (rc == COMMIT_PLAN_LDS)
+            return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits_wide: needs %zu bytes of LDS per workgroup, the device has %zu per CU", pl.lds, ctx->lds_per_cu);
+        if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_LOGITS_LDS>), dim3(pl.grid), dim3(pl.block), pl.lds, ctx->stream, d, pi_dev, v_dev);
+        else hipLaunchKernelGGL((k_commit<u32, COMMIT_LOGITS_LDS>), dim3(pl.grid), dim3(pl.block), pl.lds, ctx->stream, d, pi_dev, v_dev);
     } else {
-        if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, false>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-        else hipLaunchKernelGGL((k_commit<u32, false>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+        const dim3 grid(grid_for(d.G)), block(64 * WAVES_PER_BLOCK);  // one wave per slot; waiting slots find their evaluator row in game_row
+        const size_t lds = (size_t)WAVES_PER_BLOCK * commit_wave_lds(d.A, d.n_leaves, mode == COMMIT_LOGITS_REG ? (size_t)d.A : 0).total();
+        if (mode == COMMIT_LOGITS_REG) {
+            if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_LOGITS_REG>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+            else hipLaunchKernelGGL((k_commit<u32, COMMIT_LOGITS_REG>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+        } else {
+            if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_PROBS>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+            else hipLaunchKernelGGL((k_commit<u32, COMMIT_PROBS>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
+        }
     }
     hipError_t le_ = hipGetLastError();
     if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of k_commit failed: %s", hipGetErrorString(le_));
@@ -4675,14 +4812,19 @@ static int launch_commit(rp_ctx *ctx, const float *pi_dev, const float *v_dev, b
 
 extern "C" int rp_commit_eval(rp_ctx *ctx, const float *pi_dev, const float *v_dev) {
     if (!ctx || !pi_dev || !v_dev) return fail(ctx, RP_ERR_ARG, "rp_commit_eval: bad argument");
-    return launch_commit(ctx, pi_dev, v_dev, false);
+    return launch_commit(ctx, pi_dev, v_dev, COMMIT_PROBS);
 }
 
 extern "C" int rp_commit_eval_logits(rp_ctx *ctx, const float *logits_dev, const float *v_dev) {
     if (!ctx || !logits_dev || !v_dev) return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits: bad argument");
     if ((size_t)WAVES_PER_BLOCK * ctx->d.A * sizeof(float) > 24 * 1024)
-        return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits: %d actions do not fit the kernel's LDS row buffers (at most 1536): take the softmax first and call rp_commit_eval", ctx->d.A);
-    return launch_commit(ctx, logits_dev, v_dev, true);
+        return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits: %d actions do not fit the kernel's LDS row buffers (at most 1536): call rp_commit_eval_logits_wide, or take the softmax first and call rp_commit_eval", ctx->d.A);
+    return launch_commit(ctx, logits_dev, v_dev, COMMIT_LOGITS_REG);
+}
+
+extern "C" int rp_commit_eval_logits_wide(rp_ctx *ctx, const float *logits_dev, const float *v_dev) {
+    if (!ctx || !logits_dev || !v_dev) return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits_wide: bad argument");
+    return launch_commit(ctx, logits_dev, v_dev, COMMIT_LOGITS_LDS);
 }
 
 extern "C" int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const float *v_host, int32_t n_rows) {
@@ -4697,7 +4839,7 @@ extern "C" int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const floa
     Scratch s(ctx);
     float *dpi = s.up(pi_host, (size_t)n * d.A); NEED(dpi);
     float *dv = s.up(v_host, (size_t)n); NEED(dv);
-    { const int rc = launch_commit(ctx, dpi, dv, false); if (rc != RP_OK) return rc; }
+    { const int rc = launch_commit(ctx, dpi, dv, COMMIT_PROBS); if (rc != RP_OK) return rc; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return check_device_error(ctx);
 }

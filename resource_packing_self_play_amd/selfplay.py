@@ -40,6 +40,7 @@ class _Group:
             self.eng.set_trace(True)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
+        self.wide_logits = owner.wide_logits
         if self.use_stem:  # the engine computes the first conv + pool itself: no plane tensor at all
             self.channels_last = owner.channels_last
             self.resblock_kernel = owner.resblock_kernel
@@ -74,15 +75,23 @@ class _Group:
 
     def forward(self, nnet):
         """-> (policy rows, values).  With the fused evaluator the policy rows are the RAW logits and the softmax is taken inside the
-        commit kernel (rp_commit_eval_logits) when the action space fits its LDS row buffer."""
+        commit kernel: rp_commit_eval_logits up to LOGITS_MAX_ACTIONS, rp_commit_eval_logits_wide beyond (wide_logits; without it a
+        wide board gets torch.softmax and rp_commit_eval)."""
         if self.use_stem:
-            self.raw_logits = self.fused and self.eng.A <= self.eng.LOGITS_MAX_ACTIONS
+            self.raw_logits = self.fused and (self.eng.A <= self.eng.LOGITS_MAX_ACTIONS
+                                              or (self.wide_logits and self.eng.A <= self.eng.WIDE_LOGITS_MAX_ACTIONS))
             return nnet.predict_from_stem(self.stem, self.stem_relu, self.eng if self.fused else None, logits=self.raw_logits)
         self.raw_logits = False
         return nnet.predict_batch(self.planes)
 
     def commit(self, pi, v):
-        (self.eng.commit_eval_logits if self.raw_logits else self.eng.commit_eval)(pi.data_ptr(), v.data_ptr())
+        if not self.raw_logits:
+            commit = self.eng.commit_eval
+        elif self.eng.A <= self.eng.LOGITS_MAX_ACTIONS:
+            commit = self.eng.commit_eval_logits
+        else:
+            commit = self.eng.commit_eval_logits_wide
+        commit(pi.data_ptr(), v.data_ptr())
 
     def wave_eager(self, nnet):
         if self.host_evaluator is not None:  # generic evaluator on the host: leaf states out, (pi, v) back (like nnet.predict, MCTS_bpp.py:87)
@@ -101,8 +110,10 @@ class _Group:
 class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
-                 tie_salt=None, host_evaluator=None, record_packings=False):
-        """record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
+                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True):
+        """wide_logits: action spaces beyond Engine.LOGITS_MAX_ACTIONS hand raw logits to rp_commit_eval_logits_wide (the softmax in the
+        commit kernel, as on every smaller board); False keeps torch.softmax + rp_commit_eval for them (the A/B switch).
+        record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
         return and the finished episodes' layouts are collected for pop_packings().
         host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
@@ -120,6 +131,7 @@ class BatchedSelfPlay:
         self.compact_rows = bool(compact_rows)  # evaluator rows = the waiting slots only, listed on the device (rp_set_compact_rows)
         self.max_examples_per_group = (int(max_examples) + groups - 1) // groups if max_examples else 0
         self.tie_salt, self.host_evaluator = tie_salt, host_evaluator
+        self.wide_logits = bool(wide_logits)
         self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
         self._packings = []
         self._pool_items = None

@@ -1,0 +1,265 @@
+"""rp_commit_eval_logits_wide: the softmax of NNet.predict (NNet.py:81-85) taken inside the commit kernel with the row staged in LDS, for
+every action space of the ABI (A = W * N <= 8192; rp_commit_eval_logits keeps the row in registers and stops at 1536).
+
+(a) where both apply the two kernels' modes leave bit-identical trees -- they share the arithmetic and its order;
+(b) beyond 1536, rows whose float32 softmax has the same bits in ANY summation order against torch.softmax + rp_commit_eval, bit for bit:
+    a dropped, duplicated or misplaced element shows;
+(c) beyond 1536, random rows against a float64 reference within the float32 error of the pinned order;
+(d) the production wave of BatchedSelfPlay at 50x50 / 128 (A = 6400): raw logits reach the kernel, under graph capture and replay too."""
+import math
+import os
+
+import numpy as np
+import pytest
+
+from engine_util import tree_as_dict
+from test_gpu_mcts import gen_items, make_engine
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+WIDE_SHAPES = [(25, 10, 64), (27, 10, 60), (40, 8, 40), (64, 8, 128), (50, 50, 128)]  # A = 1600, 1620, 1600 (u64 rows), 8192, 6400 (c5)
+POLICY_TOL = 1e-5  # the project's policy tolerance
+
+
+def rel_bound(A):
+    """Relative error of a prior of the pinned float32 softmax against the float64 reference: a lane chain of ceil(A/64) - 1 adds and 6
+    butterfly adds at 2^-24 each, expf within 1 ulp once through the numerator and once through the sum, one division -- the whole
+    doubled, because the float64 renormalisation over the legal moves divides two such quantities."""
+    return 2 * (math.ceil(A / 64) + 10) * 2.0 ** -24
+
+
+def instances(W, H, N, games, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([gen_items(rng, W, H, N) for _ in range(games)])
+
+
+def commit_once(W, H, N, wh, route, logits, v):
+    """One expansion of every root (row b = slot b) through `route`; -> (tree of every slot, status, last_values)."""
+    import torch
+    from resource_packing_self_play_amd import _lib
+    games = len(wh)
+    eng = make_engine(W, H, N, games, 4, move_rule=_lib.MOVE_EXTERNAL, stream=torch.cuda.current_stream().cuda_stream)
+    eng.begin_episodes(wh, np.full(games, W * H, np.int32))
+    assert eng.search_step() == games  # every root waits for the evaluator
+    if route == "softmax":
+        pi = torch.softmax(logits, dim=1).contiguous()
+        eng.commit_eval(pi.data_ptr(), v.data_ptr())
+    elif route == "logits":
+        eng.commit_eval_logits(logits.data_ptr(), v.data_ptr())
+    else:
+        eng.commit_eval_logits_wide(logits.data_ptr(), v.data_ptr())
+    torch.cuda.synchronize()
+    status = eng.status()
+    assert (status[0] == _lib.PHASE_RUNNING).all() and (status[1] == 1).all()
+    out = [tree_as_dict(eng.dump_tree(g)) for g in range(games)], status, eng.last_values()
+    eng.close()
+    return out
+
+
+def assert_bit_equal(x, y, where):
+    trees_x, status_x, values_x = x
+    trees_y, status_y, values_y = y
+    for sx, sy in zip(status_x, status_y):
+        assert np.array_equal(sx, sy), where
+    for vx, vy in zip(values_x, values_y):
+        assert np.array_equal(vx, vy), where
+    for g, (a, b) in enumerate(zip(trees_x, trees_y)):
+        assert a.keys() == b.keys() and len(a) == 1, "%s slot %d" % (where, g)
+        for key, ra in a.items():
+            rb = b[key]
+            for f in ("es", "es_kind", "expanded", "ns"):
+                assert ra[f] == rb[f], "%s slot %d: %s" % (where, g, f)
+            for f in ("actions", "nsa", "q_kind", "child"):
+                assert np.array_equal(ra[f], rb[f]), "%s slot %d: %s" % (where, g, f)
+            for f in ("p", "q"):  # float64 bit patterns: -0.0 against 0.0 or two NaNs do not pass as equal or unequal by accident
+                fa, fb = np.ascontiguousarray(ra[f], np.float64).view(np.uint64), np.ascontiguousarray(rb[f], np.float64).view(np.uint64)
+                bad = np.flatnonzero(fa != fb)
+                assert bad.size == 0, "%s slot %d: %s differs at %d of %d legal moves, first action %d: %r vs %r" % (
+                    where, g, f, bad.size, fa.size, ra["actions"][bad[0]], ra[f][bad[0]], rb[f][bad[0]])
+
+
+@pytest.mark.parametrize("W,H,N", [(10, 10, 8), (20, 20, 32), (33, 12, 9), (24, 8, 64)])
+def test_wide_mode_is_bit_identical_to_the_register_mode(W, H, N):
+    """(a) 10x10/8, 20x20/32, 33x12/9 (u64 rows, A = 297: no multiple of 64 or of 4) and 24x8/64 (A = 1536, the last narrow size)."""
+    import torch
+    games, A = 48, W * N
+    wh = instances(W, H, N, games, W + N)
+    torch.manual_seed(W)
+    logits = (torch.randn(games, A, device="cuda") * 4.0).contiguous()
+    logits[3] = 0.0  # a flat row
+    logits[5, : A // 2] = -60.0  # probabilities that underflow to denormals / zero
+    v = torch.tanh(torch.randn(games, device="cuda")).contiguous()
+    assert_bit_equal(commit_once(W, H, N, wh, "logits", logits, v), commit_once(W, H, N, wh, "wide", logits, v), "%dx%d/%d" % (W, H, N))
+
+
+def hot_rows(A, legal_of_slot, games):
+    """Rows of k hot logits (0) among cold ones (-200): expf(-200 - 0) is exactly 0 in float32, so every float32 softmax gives
+    sum = k and p = fl(1 / k) on the hot positions, whatever its order.  -> (logits [games][A], what each row is for)."""
+    x = np.full((games, A), -200.0, np.float32)
+    what = []
+    edges = sorted({a for m in range(1024, A + 1, 1024) for a in (m - 1, m) if a < A})  # both sides of every multiple of 1024
+
+    def row(name, hot):
+        b = len(what)
+        x[b, np.asarray(sorted(set(int(a) for a in hot)), np.int64)] = 0.0
+        what.append(name)
+
+    legal = [np.asarray(legal_of_slot[b]) for b in range(games)]
+    illegal = [np.setdiff1d(np.arange(A), legal[b]) for b in range(games)]
+    row("k=1 at a=0", [0])
+    row("k=1 at a=A-1", [A - 1])
+    row("k=3: 1535, 1536, 1537", [1535, 1536, 1537])
+    row("k=A flat", range(A))
+    row("both sides of every multiple of 1024", edges)
+    row("0, 1535, 1536, 1537, A-1", [0, 1535, 1536, 1537, A - 1])
+    b = len(what); row("k=1 on a legal move", [legal[b][0]])
+    b = len(what); row("k=3 on legal moves", [legal[b][0], legal[b][len(legal[b]) // 2], legal[b][-1]])
+    b = len(what); row("legal and illegal mixed", list(legal[b][::3]) + list(illegal[b][::5]))
+    b = len(what); row("legal and illegal mixed + the 1024 edges", list(legal[b][1::2]) + list(illegal[b][::2]) + edges)
+    b = len(what); row("every hot position illegal: the uniform fallback", illegal[b][::7])
+    b = len(what); row("k=1 on an illegal move: the uniform fallback", [illegal[b][-1]])
+    b = len(what); row("k=3, the last legal move and two illegal ones", [legal[b][-1], illegal[b][0], illegal[b][-1]])
+    rng = np.random.default_rng(A)
+    while len(what) < games:
+        k = int(rng.integers(1, 200))
+        row("k=%d at random" % k, rng.choice(A, size=k, replace=False))
+    return x, what
+
+
+@pytest.mark.parametrize("W,H,N", WIDE_SHAPES)
+def test_order_independent_rows_beyond_1536_equal_the_softmax_route_bit_for_bit(W, H, N):
+    """(b)"""
+    import torch
+    games, A = 16, W * N
+    wh = instances(W, H, N, games, 3 * W + N)
+    v = torch.tanh(torch.randn(games, device="cuda", generator=torch.Generator(device="cuda").manual_seed(N))).contiguous()
+    first, _, _ = commit_once(W, H, N, wh, "softmax", torch.zeros(games, A, device="cuda"), v)  # the legal moves of every root
+    legal = [next(iter(t.values()))["actions"] for t in first]
+    assert all(0 < len(l) < A for l in legal)
+    x, what = hot_rows(A, legal, games)
+    hot_legal = [np.intersect1d(np.flatnonzero(x[b] == 0.0), legal[b]).size for b in range(games)]
+    for b in range(games):  # the rows are what they claim to be (a fixed position such as a = 0 may be legal or not)
+        if "fallback" in what[b]:
+            assert hot_legal[b] == 0, what[b]
+        if "mixed" in what[b]:
+            assert 0 < hot_legal[b] < int((x[b] == 0.0).sum()), what[b]
+    logits = torch.from_numpy(x).cuda().contiguous()
+    pi = torch.softmax(logits, dim=1)
+    k = (logits == 0).sum(dim=1, keepdim=True).float()
+    assert torch.equal(pi, torch.where(logits == 0, 1.0 / k, torch.zeros_like(pi))), "torch.softmax is not exact on these rows"
+    ref = commit_once(W, H, N, wh, "softmax", logits, v)
+    got = commit_once(W, H, N, wh, "wide", logits, v)
+    assert_bit_equal(ref, got, "%dx%d/%d" % (W, H, N))
+    for b in range(games):  # the reference itself did what the row is for (MCTS_bpp.py:93-100: uniform over the legal moves)
+        p = next(iter(ref[0][b].values()))["p"]
+        if hot_legal[b] == 0:
+            assert np.allclose(p, 1.0 / len(p), rtol=1e-15, atol=0.0), what[b]
+        else:
+            assert np.count_nonzero(p) == hot_legal[b] and np.allclose(p[p > 0], 1.0 / hot_legal[b], rtol=1e-7, atol=0.0), what[b]
+
+
+def reference_priors(x_row, actions):
+    """P over the legal moves: d = x - max in float32 as the kernel forms it, then float64 all the way."""
+    x_row = np.asarray(x_row, np.float32)
+    d = (x_row - x_row.max()).astype(np.float32)
+    e = np.exp(d.astype(np.float64))[np.asarray(actions, np.int64)]
+    return e / e.sum()
+
+
+def worst_deviation(trees, x, A):
+    worst_rel = worst_abs = 0.0
+    for b, t in enumerate(trees):
+        rec = next(iter(t.values()))
+        ref = reference_priors(x[b], rec["actions"])
+        worst_rel = max(worst_rel, float((np.abs(rec["p"] - ref) / ref).max()))
+        worst_abs = max(worst_abs, float(np.abs(rec["p"] - ref).max()))
+    return worst_rel, worst_abs
+
+
+@pytest.mark.parametrize("W,H,N", WIDE_SHAPES)
+def test_random_rows_beyond_1536_are_within_float32_rounding_of_the_float64_softmax(W, H, N):
+    """(c)  Measured worst relative deviation (MI355X), wide route / torch.softmax route: see DESIGN.md 3."""
+    import torch
+    games, A = 16, W * N
+    wh = instances(W, H, N, games, 5 * W + N)
+    gen = torch.Generator(device="cuda").manual_seed(100 + W)
+    logits = (torch.randn(games, A, device="cuda", generator=gen) * 4.0).contiguous()
+    v = torch.tanh(torch.randn(games, device="cuda", generator=gen)).contiguous()
+    x = logits.cpu().numpy()
+    assert float((x - x.max(axis=1, keepdims=True)).min()) > -80.0  # every exponential is a normal float32: no entry needs excluding
+    wide = worst_deviation(commit_once(W, H, N, wh, "wide", logits, v)[0], x, A)
+    lib = worst_deviation(commit_once(W, H, N, wh, "softmax", logits, v)[0], x, A)
+    print("%dx%d/%d (A = %d): worst relative deviation of a prior from the float64 softmax: wide route %.3e, torch.softmax route %.3e "
+          "(bound %.3e); absolute %.3e / %.3e" % (W, H, N, A, wide[0], lib[0], rel_bound(A), wide[1], lib[1]))
+    assert wide[0] <= rel_bound(A)
+    assert wide[1] <= POLICY_TOL
+
+
+def seeded_wrapper(d):
+    """test_gpu_nnet.gpu_wrapper for a fixture that keeps a seed instead of weights (nnet_c5_seed0.npz: 50x50 / 128 is too large to store):
+    the network is torch.manual_seed(seed)'s initialisation.  Nothing here depends on the fixture's recorded outputs."""
+    import torch
+    from resource_packing_self_play_amd.binpacking.BinPackingGame import BinPackingGame
+    from resource_packing_self_play_amd.binpacking.pytorch.NNet import NNetWrapper
+    from resource_packing_self_play_amd.utils import dotdict
+    W, H, N = int(d["W"]), int(d["H"]), int(d["N"])
+    args = dotdict(dict(cuda=True, num_items=N, num_bins=1, epochs=1, batch_size=8, numMCTSSims=20, cpuct=1, alpha=0.75))
+    game = BinPackingGame(W, H, N, 1)
+    torch.manual_seed(int(d["seed"]))
+    return game, NNetWrapper(game, args), args
+
+
+def test_production_wave_at_c5_takes_the_softmax_in_the_commit_kernel():
+    """(d)"""
+    import torch
+    from resource_packing_self_play_amd import _lib
+    from resource_packing_self_play_amd.selfplay import BatchedSelfPlay
+    d = np.load(os.path.join(GOLDEN, "nnet_c5_seed0.npz"))
+    game, net, args = seeded_wrapper(d)
+    args.numMCTSSims, args.cpuct, args.alpha = 6, 1, 0.75
+    A = game.bin_width * game.num_items
+    assert A == 6400 > _lib.Engine.LOGITS_MAX_ACTIONS
+    seeds = np.arange(6, dtype=np.uint32) + 900
+    games = 6
+
+    def driver(**kw):
+        return BatchedSelfPlay(game, net, args, games=games, move_rule=_lib.MOVE_SAMPLE, seed=7, groups=1, **kw)
+
+    # the first wave: every slot waits at its root, so row b belongs to slot b
+    sp = driver()
+    sp.prepare()
+    sp.start_from_seeds(seeds, rewards_list=[0.9, 0.95, 1.0])
+    sp.step()
+    torch.cuda.synchronize()
+    g = sp.groups[0]
+    assert g.raw_logits is True
+    x = g.pi.cpu().numpy()
+    assert x.shape == (games, A)
+    sums = x.astype(np.float64).sum(axis=1)
+    assert (np.abs(sums - 1.0) > 1e-3).all(), "groups[0].pi holds probabilities, not raw logits: %r" % sums
+    for b in range(games):
+        tree = tree_as_dict(sp.eng.dump_tree(b))
+        roots = [rec for rec in tree.values() if rec["expanded"]]
+        assert len(roots) == 1
+        ref = reference_priors(x[b], roots[0]["actions"])
+        rel = np.abs(roots[0]["p"] - ref) / ref
+        assert float((x[b] - x[b].max()).min()) > -80.0
+        assert float(rel.max()) <= rel_bound(A), "slot %d: %.3e" % (b, float(rel.max()))
+    sp.close()
+
+    # whole pools: captured graph against eager launches, then the torch.softmax route
+    res = {}
+    for name, kw in (("graph", dict(use_graph=True)), ("eager", dict(use_graph=False)), ("softmax", dict(wide_logits=False))):
+        sp = driver(**kw)
+        sp.prepare()
+        out = sp.run_from_seeds(seeds, rewards_list=[0.9, 0.95, 1.0])
+        assert sp.groups[0].raw_logits is (name != "softmax")
+        assert len(out[0]) == len(seeds)
+        res[name] = out[:4] + (np.array([out[4][k] for k in ("simulations", "expansions", "path_edges", "nodes")]),)
+        sp.close()
+    for a, b in zip(res["graph"], res["eager"]):
+        assert np.array_equal(a, b)
+    assert len(res["softmax"][0]) == len(res["graph"][0]) and res["softmax"][4][0] == res["graph"][4][0]
+    print("c5 pool, torch.softmax route against the wide route: scores %s, moves %s" % (
+        "equal" if np.array_equal(res["softmax"][2], res["graph"][2]) else "differ",
+        "equal" if np.array_equal(res["softmax"][3], res["graph"][3]) else "differ"))
