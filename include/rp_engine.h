@@ -33,9 +33,10 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 6  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+#define RP_ABI_VERSION 7  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
                              5: placement trace (rp_set_trace, rp_pop_finished_packings)
-                             6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan) */
+                             6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan)
+                             7: the commit kernel's softmax as a self-test (rp_selftest_softmax) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -363,6 +364,10 @@ int rp_selftest_q_update(rp_ctx *ctx, int64_t n, const double *q, const uint8_t 
                          const double *v, const uint8_t *v_kind, double *q_out, uint8_t *q_kind_out);
 int rp_selftest_masked_prior(rp_ctx *ctx, int64_t B, const float *pi /*[B][A]*/, const uint8_t *valid /*[B][A]*/,
                              double *p_out /*[B][A]*/);
+/* The softmax that rp_commit_eval_logits (wide == 0: the row in registers, RP_ERR_ARG beyond 1536 actions) and rp_commit_eval_logits_wide
+ * (wide != 0: the row in LDS, every action space) take inside the commit kernel, from the same device helpers in the same order, one wave
+ * per row; tests/test_gpu_commit_wide.py holds the commit kernel's priors to it bit for bit. */
+int rp_selftest_softmax(rp_ctx *ctx, int64_t B, const float *logits /*[B][A]*/, int32_t wide, float *pi_out /*[B][A]*/);
 
 #ifdef __cplusplus
 }

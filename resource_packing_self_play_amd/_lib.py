@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -104,6 +104,7 @@ _SIGS = {
     "rp_selftest_sqrt": (C.c_int, [_vp, _i64, _vp, _vp]),
     "rp_selftest_q_update": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_selftest_masked_prior": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "rp_selftest_softmax": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
 }
 _lib = None
 
@@ -572,4 +573,13 @@ class Engine:
         pi = _arr(pi, np.float32, (B, self.A)); valid = _arr(valid, np.uint8, (B, self.A))
         out = np.empty((B, self.A), np.float64)
         self._ck(self.L.rp_selftest_masked_prior(self.h, B, _ptr(pi), _ptr(valid), _ptr(out)))
+        return out
+
+    def selftest_softmax(self, logits, wide):
+        """The commit kernel's own softmax of every row (rp_selftest_softmax): wide False = the register form of commit_eval_logits
+        (EngineError beyond LOGITS_MAX_ACTIONS), True = the LDS form of commit_eval_logits_wide.  -> float32 [B, A]."""
+        logits = _arr(logits, np.float32); B = logits.shape[0]
+        logits = _arr(logits, np.float32, (B, self.A))
+        out = np.empty((B, self.A), np.float32)
+        self._ck(self.L.rp_selftest_softmax(self.h, B, _ptr(logits), 1 if wide else 0, _ptr(out)))
         return out

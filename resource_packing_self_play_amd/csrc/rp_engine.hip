@@ -2304,6 +2304,48 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_selftest_prior(DP p, l
     wave_sync();
     for (int k = lane; k < nv; k += 64) o[act[k]] = Tree<u32>::prior_of(pc[k], norm, fb);
 }
+// k_commit's softmax on its own (rp_selftest_softmax): one wave per row, written from the pieces the two logits modes of k_commit share
+// (softmax_exp, softmax_div, wave_max, wave_sum, stage_logits_row) in the order pinned above k_commit -- lane l owns a = l + 64 i, adds its
+// exponentials in ascending i, the butterfly o = 32 ... 1 joins the lanes.  WIDE = 0 is COMMIT_LOGITS_REG's form (the row in 24 registers per
+// lane, WAVES_PER_BLOCK rows per workgroup), WIDE = 1 COMMIT_LOGITS_LDS's (the row staged in LDS, one row per workgroup).  Moving the two
+// blocks of k_commit into functions called from both kernels cost COMMIT_LOGITS_REG 21 VGPRs and two waves per SIMD, so k_commit keeps its
+// text; tests/test_gpu_commit_wide.py holds the trees k_commit leaves to this kernel's output bit for bit.
+template <int WIDE>
+__global__ void __launch_bounds__(WIDE ? 64 : 64 * WAVES_PER_BLOCK) k_selftest_softmax(int A, long long B, const float *logits, float *out) {
+    extern __shared__ __attribute__((aligned(16))) float s_row[];
+    const int wv = WIDE ? 0 : wave_in_block(), lane = lane_id();
+    const long long b = WIDE ? (long long)blockIdx.x : (long long)blockIdx.x * WAVES_PER_BLOCK + wv;
+    if (b >= B) return;
+    const float *row = logits + b * A;
+    float *sp = s_row + (size_t)wv * A;
+    if (WIDE) {
+        float m = stage_logits_row(row, sp, A, lane);  // pass 1
+        m = wave_max(m);
+        lds_sync();
+        float sum = 0.f;
+        for (int a = lane; a < A; a += 64) { const float e = softmax_exp(sp[a], m); sp[a] = e; sum += e; }  // pass 2
+        sum = wave_sum(sum);
+        for (int a = lane; a < A; a += 64) sp[a] = softmax_div(sp[a], sum);  // pass 3
+    } else {
+        constexpr int LPL = 24;
+        float xr[LPL];
+#pragma unroll
+        for (int i = 0; i < LPL; ++i) { const int a = lane + 64 * i; xr[i] = (64 * i < A && a < A) ? row[a] : -INFINITY; }
+        float m = xr[0];
+#pragma unroll
+        for (int i = 1; i < LPL; ++i) m = fmaxf(m, xr[i]);
+        m = wave_max(m);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < LPL; ++i)
+            if (64 * i < A) { xr[i] = softmax_exp(xr[i], m); sum += xr[i]; }
+        sum = wave_sum(sum);
+#pragma unroll
+        for (int i = 0; i < LPL; ++i) { const int a = lane + 64 * i; if (64 * i < A && a < A) sp[a] = softmax_div(xr[i], sum); }
+    }
+    wave_sync();
+    for (int a = lane; a < A; a += 64) out[b * A + a] = sp[a];
+}
 
 // ------------------------------------------------------------------------------------------------
 // Fused element-wise pieces of the evaluator (BinpackingNNet.py:21-27,39-40).  PyTorch-ROCm runs a convolution's bias add,
@@ -5268,6 +5310,26 @@ extern "C" int rp_selftest_masked_prior(rp_ctx *ctx, int64_t B, const float *pi,
                        (const u8 *)dva, dout, dact, dpc);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(p_out, dout, (size_t)B * d.A * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RP_OK;
+}
+
+extern "C" int rp_selftest_softmax(rp_ctx *ctx, int64_t B, const float *logits, int32_t wide, float *pi_out) {
+    if (!ctx || B < 0 || !logits || !pi_out) return fail(ctx, RP_ERR_ARG, "rp_selftest_softmax: bad argument");
+    const DP &d = ctx->d;
+    if (!wide && d.A > 1536) return fail(ctx, RP_ERR_ARG, "rp_selftest_softmax: the register form holds at most 1536 actions, not %d", d.A);
+    if (B == 0) return RP_OK;
+    Scratch s(ctx);
+    float *dx = s.up(logits, (size_t)B * d.A); NEED(dx);
+    float *dout = s.up((const float *)nullptr, (size_t)B * d.A); NEED(dout);
+    if (wide)  // one row of at most 8192 floats (the row 16-byte aligned like k_commit's): 32 KB, below the default limit
+        hipLaunchKernelGGL(k_selftest_softmax<1>, dim3((unsigned)B), dim3(64), (size_t)((d.A + 3) & ~3) * sizeof(float), ctx->stream, d.A, (long long)B,
+                           (const float *)dx, dout);
+    else  // WAVES_PER_BLOCK rows of at most 1536 floats
+        hipLaunchKernelGGL(k_selftest_softmax<0>, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), (size_t)WAVES_PER_BLOCK * d.A * sizeof(float), ctx->stream,
+                           d.A, (long long)B, (const float *)dx, dout);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(pi_out, dout, (size_t)B * d.A * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RP_OK;
 }

@@ -5,13 +5,16 @@ every action space of the ABI (A = W * N <= 8192; rp_commit_eval_logits keeps th
 (b) beyond 1536, rows whose float32 softmax has the same bits in ANY summation order against torch.softmax + rp_commit_eval, bit for bit:
     a dropped, duplicated or misplaced element shows;
 (c) beyond 1536, random rows against a float64 reference within the float32 error of the pinned order;
-(d) the production wave of BatchedSelfPlay at 50x50 / 128 (A = 6400): raw logits reach the kernel, under graph capture and replay too."""
+(d) the production wave of BatchedSelfPlay at 50x50 / 128 (A = 6400): raw logits reach the kernel, under graph capture and replay too;
+(e) the priors either mode leaves in the tree are, bit for bit, the NumPy-order masked prior of rp_selftest_softmax's output, and that output
+    is within float32 rounding of the float64 softmax element by element: the logits commit pinned exactly, not to 2e-6 of a library."""
 import math
 import os
 
 import numpy as np
 import pytest
 
+import oracle_lib as orc
 from engine_util import tree_as_dict
 from test_gpu_mcts import gen_items, make_engine
 
@@ -193,6 +196,120 @@ def test_random_rows_beyond_1536_are_within_float32_rounding_of_the_float64_soft
           "(bound %.3e); absolute %.3e / %.3e" % (W, H, N, A, wide[0], lib[0], rel_bound(A), wide[1], lib[1]))
     assert wide[0] <= rel_bound(A)
     assert wide[1] <= POLICY_TOL
+
+
+NARROW_SHAPES = [(10, 10, 8), (20, 20, 32), (33, 12, 9), (24, 8, 64)]
+
+
+def host_masked_prior(pi_row, actions):
+    """P = pi * valids; P /= np.sum(P), or uniform over the legal moves (MCTS_bpp.py:89-100), as test_masked_prior_matches_numpy forms it:
+    float64 products, NumPy's pairwise sum, one division per move.  -> (P of the legal moves in `actions` order, fallback taken)."""
+    valid = np.zeros(len(pi_row), np.int64)
+    valid[np.asarray(actions, np.int64)] = 1
+    P = np.asarray(pi_row, np.float32) * valid
+    assert P.dtype == np.float64
+    s = orc.np_sum(P)
+    fallback = not s > 0
+    if fallback:
+        P = P + valid
+        s = orc.np_sum(P)
+    P = P / s
+    return P[np.asarray(actions, np.int64)], fallback
+
+
+def elementwise_bound(A):
+    """rel_bound without its doubling: one element of the float32 softmax against the float64 one, not a ratio of two such quantities."""
+    return (math.ceil(A / 64) + 10) * 2.0 ** -24
+
+
+def check_exported_softmax(W, H, N, wh, x, modes, want_fallback):
+    """x [games][A] float32 logits, row b for slot b.  -> number of rows held to the float64 softmax."""
+    import torch
+    games, A = x.shape
+    logits = torch.from_numpy(x).cuda().contiguous()
+    v = torch.tanh(torch.randn(games, device="cuda", generator=torch.Generator(device="cuda").manual_seed(A))).contiguous()
+    eng = make_engine(W, H, N, 1, 4)
+    pis = {wide: eng.selftest_softmax(x, wide) for wide in modes}
+    eng.close()
+    if len(modes) == 2:
+        assert np.array_equal(pis[0].view(np.uint32), pis[1].view(np.uint32)), "register and LDS form of the exported softmax differ"
+    fallbacks = 0
+    for wide in modes:
+        pi = pis[wide]
+        assert pi.shape == (games, A) and pi.dtype == np.float32
+        trees, _, _ = commit_once(W, H, N, wh, "wide" if wide else "logits", logits, v)
+        for b, t in enumerate(trees):
+            rec = next(iter(t.values()))
+            want, fb = host_masked_prior(pi[b], rec["actions"])
+            fallbacks += fb
+            got = np.ascontiguousarray(rec["p"], np.float64).view(np.uint64)
+            bad = np.flatnonzero(got != np.ascontiguousarray(want, np.float64).view(np.uint64))
+            assert bad.size == 0, "%dx%d/%d wide=%d slot %d: %d of %d priors differ from the masked prior of the exported softmax, first %r vs %r" % (
+                W, H, N, wide, b, bad.size, got.size, rec["p"][bad[0]], want[bad[0]])
+    assert (fallbacks > 0) == want_fallback, fallbacks
+    # element by element against float64: rows whose exponentials (and quotients) are all normal float32 numbers
+    d = (x - x.max(axis=1, keepdims=True)).astype(np.float32)
+    e = np.exp(d.astype(np.float64))
+    ref = e / e.sum(axis=1, keepdims=True)
+    normal = (d.min(axis=1) > -80.0) & (ref.min(axis=1) >= 2.0 ** -126)
+    for wide in modes:
+        rel = np.abs(pis[wide][normal].astype(np.float64) - ref[normal]) / ref[normal]
+        print("%dx%d/%d (A = %d) wide=%d: %d rows, worst relative deviation of an element from the float64 softmax %.3e (bound %.3e)" % (
+            W, H, N, A, wide, int(normal.sum()), float(rel.max()) if rel.size else 0.0, elementwise_bound(A)))
+        assert rel.size == 0 or float(rel.max()) <= elementwise_bound(A)
+    return normal
+
+
+def random_rows(games, A, seed, legal=None):
+    """randn * 4 with a flat row (3), a row with half its entries at -60 (5) and, given the legal moves of slot 7, a row that is cold on all of
+    them: the uniform fallback."""
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((games, A)) * 4.0).astype(np.float32)
+    x[3] = 0.0
+    x[5, : A // 2] = -60.0
+    if legal is not None:
+        x[7] = 0.0
+        x[7, np.asarray(legal[7], np.int64)] = -200.0
+    return x
+
+
+def legal_moves(W, H, N, wh):
+    import torch
+    games = len(wh)
+    first, _, _ = commit_once(W, H, N, wh, "softmax", torch.zeros(games, W * N, device="cuda"), torch.zeros(games, device="cuda"))
+    legal = [next(iter(t.values()))["actions"] for t in first]
+    assert all(0 < len(l) < W * N for l in legal)
+    return legal
+
+
+@pytest.mark.parametrize("W,H,N", NARROW_SHAPES)
+def test_committed_priors_are_the_masked_prior_of_the_exported_softmax(W, H, N):
+    """(e) up to 1536 actions, both modes: 48 slots, randn * 4, a flat row, a half -60 row, a row that takes the uniform fallback."""
+    games, A = 48, W * N
+    wh = instances(W, H, N, games, W + N)
+    x = random_rows(games, A, 7 * W + N, legal_moves(W, H, N, wh))
+    normal = check_exported_softmax(W, H, N, wh, x, (0, 1), want_fallback=True)
+    assert normal[:7].all() and not normal[7] and normal[8:].all()  # every row but the fallback one (-200) meets the > -80 precondition
+
+
+@pytest.mark.parametrize("W,H,N", WIDE_SHAPES)
+def test_committed_priors_beyond_1536_are_the_masked_prior_of_the_exported_softmax(W, H, N):
+    """(e) beyond 1536 actions, LDS form: 16 slots of random rows (flat and half -60 among them), then the 16 hot rows of (b) with their
+    fallback rows; the register form refuses the shape."""
+    from resource_packing_self_play_amd import _lib
+    games, A = 16, W * N
+    wh = instances(W, H, N, games, 3 * W + N)
+    normal = check_exported_softmax(W, H, N, wh, random_rows(games, A, 11 * W + N), (1,), want_fallback=False)
+    assert normal.all()
+    x, what = hot_rows(A, legal_moves(W, H, N, wh), games)
+    assert any("fallback" in w for w in what)
+    normal = check_exported_softmax(W, H, N, wh, x, (1,), want_fallback=True)
+    assert [w for w, n in zip(what, normal) if n] == ["k=A flat"]  # -200 next to 0 is below the precondition everywhere else
+    eng = make_engine(W, H, N, 1, 4)
+    with pytest.raises(_lib.EngineError) as ei:
+        eng.selftest_softmax(x, 0)
+    assert ei.value.code == _lib.ERR_ARG
+    eng.close()
 
 
 def seeded_wrapper(d):
