@@ -33,10 +33,11 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 7  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+#define RP_ABI_VERSION 8  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
                              5: placement trace (rp_set_trace, rp_pop_finished_packings)
                              6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan)
-                             7: the commit kernel's softmax as a self-test (rp_selftest_softmax) */
+                             7: the commit kernel's softmax as a self-test (rp_selftest_softmax)
+                             8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -270,6 +271,29 @@ int rp_commit_eval_logits(rp_ctx *ctx, const float *logits_dev, const float *v_d
 int rp_commit_eval_logits_wide(rp_ctx *ctx, const float *logits_dev, const float *v_dev);
 /* Same with HOST float32 buffers (tests, CPU evaluators). */
 int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const float *v_host, int32_t n_rows);
+
+/* ---- network-free evaluator: uniform random playouts in place of nnet.predict (MCTS_bpp.py:87) ---- */
+/* Playout j from state S = (rows, remaining) of the episode with id e draws from h0 = mix64(key_hash(S, seed) ^ e): key_hash is the
+ * sequential splitmix64 over the salt (here rp_config.seed), the H row masks, then the remaining-item words -- the hash of the tie
+ * rule.  At step s = 0, 1, ... it counts the legal moves nv (getValidMoves, BinPackingGame.py:78-92); nv == 0 ends the playout,
+ * otherwise it plays legal move number umulhi(sample(h0, j, s), nv) in ascending action order (a = item * W + column) through
+ * execute_move (BinPackingLogic.py:95-109), sample(seed, episode, move) being the RP_MOVE_SAMPLE stream
+ * mix64(mix64(mix64(seed) ^ episode) ^ move).  Every move places one item, so a playout has at most N steps.  Its outcome is
+ * getRankedReward (BinPackingGame.py:188-212) of the final bin against the episode's R2 threshold, total area and max_h, the r == bl
+ * tie resolved from the final state and rp_config.tie_salt exactly as the search resolves Es; its score is r.  A function of (state,
+ * episode items, episode id, threshold, seed, tie salt) only: not of the slot, the evaluator row, the group or the launch. */
+/* MCTS_bpp.py:87 for the leaves waiting for evaluation: v_dev[b] = float32(sum of the `playouts` outcomes) / float32(playouts), row b as
+ * in rp_leaf_planes, and -- when pi_dev != NULL -- pi_dev row b = float32(1) / float32(W * N) in every entry (the uniform prior;
+ * rp_commit_eval masks and renormalises it).  DEVICE float32 buffers of capacity_rows rows.  Enqueues one kernel only: capturable.
+ * 1 <= playouts <= 256, else RP_ERR_ARG. */
+int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev /* may be NULL */, float *v_dev, int64_t capacity_rows);
+/* The same playouts (MCTS_bpp.py:87) over a batch of B host states, `playouts` each, with everything they produce: the resolved outcome
+ * (+-1), the score r, the moves played (0 for a state without a legal move) and the final bin's row masks (board_out may be NULL).
+ * episode_id NULL: every state plays as episode 0; rewards / alpha: the R2 buffer shared by the batch, as rp_game_ended takes it. */
+int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
+                      const int32_t *total_area, const int32_t *max_h, const uint64_t *episode_id /* NULL: 0 */,
+                      const double *rewards, int32_t n_rewards, double alpha, int32_t playouts,
+                      int32_t *outcome_out /*[B][playouts]*/, double *score_out, int32_t *moves_out, uint64_t *board_out /*[B][playouts][H]*/);
 
 /* ---- results ------------------------------------------------------------------------- */
 /* counts[a] = Nsa[(root, a)] (MCTS_bpp.py:40-41), host buffer [count][W*N] */

@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -82,6 +82,8 @@ _SIGS = {
     "rp_commit_eval_logits": (C.c_int, [_vp, _vp, _vp]),
     "rp_commit_eval_logits_wide": (C.c_int, [_vp, _vp, _vp]),
     "rp_commit_eval_host": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "rp_rollout_eval": (C.c_int, [_vp, _i32, _vp, _vp, _i64]),
+    "rp_rollout_states": (C.c_int, [_vp, _i64] + [_vp] * 7 + [_i32, _f64, _i32] + [_vp] * 4),
     "rp_root_counts": (C.c_int, [_vp, _i32, _i32, _vp]),
     "rp_game_status": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rp_advance_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
@@ -456,6 +458,30 @@ class Engine:
 
     def commit_eval(self, pi_dev_ptr, v_dev_ptr):
         self._ck(self.L.rp_commit_eval(self.h, C.c_void_p(pi_dev_ptr), C.c_void_p(v_dev_ptr)))
+
+    MAX_PLAYOUTS = 256  # rp_rollout_eval / rp_rollout_states
+
+    def rollout_eval(self, v_ptr, capacity_rows, playouts, pi_ptr=None):
+        """Random-playout evaluator of the waiting leaves (rp_rollout_eval): v[b] = mean outcome of `playouts` uniform random playouts,
+        and -- with pi_ptr -- pi row b = 1 / A.  Device pointers of capacity_rows rows; enqueues only."""
+        self._ck(self.L.rp_rollout_eval(self.h, int(playouts), C.c_void_p(pi_ptr) if pi_ptr else None, C.c_void_p(v_ptr), int(capacity_rows)))
+
+    def rollout_states(self, rows, remaining, item_wh, total_area, max_h, rewards, alpha, playouts, episode_id=None, boards=True):
+        """`playouts` uniform random playouts from each of B host states (rp_rollout_states) -> (outcome int32 [B, K], score float64
+        [B, K], moves int32 [B, K], final bins uint64 [B, K, H] or None without `boards`)."""
+        rows = _arr(rows, np.uint64); B = rows.shape[0]; K = int(playouts)
+        rows = _arr(rows, np.uint64, (B, self.H)); remaining = _arr(remaining, np.uint8, (B, self.N))
+        item_wh = _arr(item_wh, np.uint8, (B, self.N, 2))
+        total_area = _arr(total_area, np.int32, (B,)); max_h = _arr(max_h, np.int32, (B,))
+        ids = None if episode_id is None else _arr(episode_id, np.uint64, (B,))
+        rewards = _arr(rewards, np.float64).reshape(-1)
+        Kc = max(K, 0)
+        outcome = np.zeros((B, Kc), np.int32); score = np.zeros((B, Kc), np.float64); moves = np.zeros((B, Kc), np.int32)
+        board = np.zeros((B, Kc, self.H), np.uint64) if boards else None
+        self._ck(self.L.rp_rollout_states(self.h, B, _ptr(rows), _ptr(remaining), _ptr(item_wh), _ptr(total_area), _ptr(max_h), _ptr(ids),
+                                          _ptr(rewards) if rewards.size else None, rewards.size, float(alpha), K, _ptr(outcome), _ptr(score),
+                                          _ptr(moves), _ptr(board)))
+        return outcome, score, moves, board
 
     LOGITS_MAX_ACTIONS = 1536  # rp_commit_eval_logits keeps a row in registers, 24 elements per lane
     WIDE_LOGITS_MAX_ACTIONS = 8192  # rp_commit_eval_logits_wide keeps it in LDS: every action space of the ABI

@@ -428,12 +428,16 @@ __device__ int ranked_reward(row_t myrow, int H, int W, int total_area, int max_
 // deterministic stand-in for np.random.choice([1,-1]) (BinPackingGame.py:212): sequential splitmix64 over
 // the row masks and the remaining-item words (tests/evaluators.py tie_value computes the same).
 template <typename row_t>
-__device__ int tie_value(row_t myrow, int H, int N, u64 rem0, u64 rem1, u64 salt) {
+__device__ u64 key_hash(row_t myrow, int H, int N, u64 rem0, u64 rem1, u64 salt) {
     u64 h = mix64(salt);
     for (int r = 0; r < H; ++r) h = mix64(h ^ (u64)RowOps<row_t>::at(myrow, r));
     h = mix64(h ^ rem0);
     if (N > 64) h = mix64(h ^ rem1);
-    return (mix64(h ^ 0x7469ull) & 1ull) ? 1 : -1;
+    return h;
+}
+template <typename row_t>
+__device__ int tie_value(row_t myrow, int H, int N, u64 rem0, u64 rem1, u64 salt) {
+    return (mix64(key_hash<row_t>(myrow, H, N, rem0, rem1, salt) ^ 0x7469ull) & 1ull) ? 1 : -1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2257,6 +2261,133 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_game_ended(DP p, long 
     int e = 0;
     if (nv == 0) e = ranked_reward<row_t>(myrow, p.H, p.W, area[b], max_h[b], has_buf != 0, bl, &r);
     if (lane_id() == 0) { ended[b] = e; reward[b] = r; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Random-playout leaf evaluator: stands in for nnet.predict (MCTS_bpp.py:87) without a network.  Playout j of state S in episode e
+// draws from h0 = mix64(key_hash(S, seed) ^ e): at step s it plays legal move number umulhi(sample_u64(h0, j, s), nv) in ascending
+// action order until no legal move is left -- every move places one item, so N steps bound the loop -- and its outcome is the final
+// bin's ranked reward against the slot's R2 threshold, the r == bl tie resolved by tie_value as the search resolves Es.  A function
+// of (state, items, episode id, threshold, seed, tie salt) only: not of the slot, the evaluator row or the launch shape.
+// One wave per playout.  gen_valid_moves with neither list nor mask leaves the per-item column masks in the wave's VM_WORDS LDS
+// words; lanes = items then find the picked move with a popcount prefix and an n-th set bit on the owning item's mask, so the action
+// list is never written.  Returns the final state through myrow / rem0 / rem1 and the number of moves played.
+// ------------------------------------------------------------------------------------------------
+struct ItemSizes { int w_lo, h_lo, w_hi, h_hi; };  // sizes of items lane and 64 + lane
+template <bool BIG> __device__ __forceinline__ ItemSizes load_item_sizes(const u8 *wh, int N) {
+    const int lane = lane_id();
+    ItemSizes z = {0, 0, 0, 0};
+    if (lane < N) { z.w_lo = wh[2 * lane]; z.h_lo = wh[2 * lane + 1]; }
+    if (BIG && lane + 64 < N) { z.w_hi = wh[2 * (lane + 64)]; z.h_hi = wh[2 * (lane + 64) + 1]; }
+    return z;
+}
+template <typename row_t, bool BIG>
+__device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row_t &myrow, u64 &rem0, u64 &rem1, u64 h0, u64 j, u64 *vm) {
+    const int lane = lane_id(), N = p.N;
+    const bool big = BIG && N > 64;
+    ValidSink sink;
+    sink.act = nullptr; sink.mask = nullptr; sink.cap = 0; sink.vm = vm;
+    sink.have_sizes = 1; sink.w_lo = z.w_lo; sink.h_lo = z.h_lo; sink.w_hi = z.w_hi; sink.h_hi = z.h_hi;
+    int moves = 0;
+    for (int s = 0; s < N; ++s) {
+        const int nv = gen_valid_moves<row_t, BIG>(p, wh, myrow, rem0, rem1, sink);
+        if (nv <= 0) break;
+        const u64 m_lo = vm[lane], m_hi = big ? vm[64 + lane] : 0ull;
+        lds_sync();  // the masks are in registers before the next gen_valid_moves clears the words
+        const int pick = (int)__umul64hi(sample_u64(h0, j, (u64)s), (u64)nv);  // 0 <= pick < nv
+        const int inc_lo = (int)wave_scan_add((u32)__popcll(m_lo));
+        const int tot_lo = __builtin_amdgcn_readlane(inc_lo, 63);
+        int item, skip;  // the item that owns legal move `pick`, and how many of its columns come before it
+        u64 own;
+        if (pick < tot_lo) {
+            const int l = __ffsll((long long)__ballot(pick < inc_lo)) - 1;  // first item whose inclusive count exceeds pick
+            item = l;
+            skip = pick - (__builtin_amdgcn_readlane(inc_lo, l) - __popcll(uni(__shfl(m_lo, l))));
+            own = uni(__shfl(m_lo, l));
+        } else {
+            const int inc_hi = (int)wave_scan_add((u32)__popcll(m_hi)), q = pick - tot_lo;
+            const int l = __ffsll((long long)__ballot(q < inc_hi)) - 1;
+            item = 64 + l;
+            skip = q - (__builtin_amdgcn_readlane(inc_hi, l) - __popcll(uni(__shfl(m_hi, l))));
+            own = uni(__shfl(m_hi, l));
+        }
+        for (int k = 0; k < skip; ++k) own &= own - 1;  // skip < popcount(own) <= 64
+        const int col = __ffsll((long long)own) - 1;
+        const int w = item < 64 ? __builtin_amdgcn_readlane(z.w_lo, item & 63) : __builtin_amdgcn_readlane(z.w_hi, item & 63);
+        const int h = item < 64 ? __builtin_amdgcn_readlane(z.h_lo, item & 63) : __builtin_amdgcn_readlane(z.h_hi, item & 63);
+        myrow = apply_move_rows<row_t>(myrow, p.H, p.W, col, w, h);
+        if (item < 64) rem0 &= ~(1ull << item); else rem1 &= ~(1ull << (item - 64));
+        ++moves;
+    }
+    return moves;
+}
+// ranked outcome of a finished playout: +-1, the r == bl tie drawn from the final state like Es (Tree::materialize); *r_out = r
+template <typename row_t>
+__device__ int playout_outcome(const DP &p, row_t myrow, u64 rem0, u64 rem1, int total_area, int max_h, bool has_buf, double bl, double *r_out) {
+    int e = ranked_reward<row_t>(myrow, p.H, p.W, total_area, max_h, has_buf, bl, r_out);
+    if (e == 2) e = tie_value<row_t>(myrow, p.H, p.N, rem0, rem1, p.tie_salt);
+    return e;
+}
+
+// Leaves waiting for evaluation -> v[b] = float32(sum of K outcomes) / float32(K), and pi row b = 1 / A when pi != NULL.  One workgroup
+// per evaluator row (the mapping of k_leaf_planes), its waves take playouts wave, wave + WAVES_PER_BLOCK, ...; the outcomes are summed
+// as integers through LDS behind one barrier.  Every exit condition depends on the row alone, so it is workgroup-uniform.
+template <typename row_t, bool BIG>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int playouts, float *pi, float *v, long long capacity_rows) {
+    const int b = blockIdx.x, wv = wave_in_block();
+    if (b >= (p.rows_identity ? p.G : *p.eval_count) || b >= capacity_rows) return;
+    const int g = __builtin_amdgcn_readfirstlane(p.rows_identity ? b : p.eval_slot[b]);
+    if (p.phase[g] != RP_PHASE_WAIT_EVAL) return;
+    __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
+    __shared__ int s_sum[WAVES_PER_BLOCK];
+    Tree<row_t, BIG> t(p, g);
+    row_t leaf; u64 l0, l1;
+    t.load_key(p.leaf_node[g], leaf, l0, l1);
+    const ItemSizes z = load_item_sizes<BIG>(t.wh, p.N);
+    const int area = p.total_area[g], max_h = p.max_h[g];
+    const bool has_buf = p.has_buf[g] != 0;
+    const double bl = p.bl[g];
+    const u64 h0 = mix64(key_hash<row_t>(leaf, p.H, p.N, l0, l1, p.seed) ^ p.episode[g]);
+    int sum = 0;
+    for (int j = wv; j < playouts; j += WAVES_PER_BLOCK) {
+        row_t myrow = leaf; u64 rem0 = l0, rem1 = l1;
+        random_playout<row_t, BIG>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
+        double r;
+        sum += playout_outcome<row_t>(p, myrow, rem0, rem1, area, max_h, has_buf, bl, &r);
+    }
+    if (lane_id() == 0) s_sum[wv] = sum;
+    if (pi) {
+        const float u = 1.0f / (float)p.A;
+        float *row = pi + (size_t)b * p.A;
+        for (int a = threadIdx.x; a < p.A; a += 64 * WAVES_PER_BLOCK) row[a] = u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int k = 0; k < WAVES_PER_BLOCK; ++k) tot += s_sum[k];
+        v[b] = (float)tot / (float)playouts;
+    }
+}
+// The stateless batch form: one wave per (state, playout) of B host states, K playouts each.
+template <typename row_t, bool BIG>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh,
+                                                                          const int *area, const int *max_h, const u64 *episode, int has_buf, double bl,
+                                                                          int *outcome, double *score, int *moves_out, u64 *board) {
+    const long long idx = (long long)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
+    if (idx >= B * playouts) return;
+    const long long b = idx / playouts;
+    const int j = (int)(idx - b * playouts), lane = lane_id();
+    __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
+    row_t myrow; u64 rem0, rem1;
+    load_host_state<row_t>(p, rows + b * p.H, rem + b * p.N, myrow, rem0, rem1);
+    const u8 *w2 = wh + b * p.N * 2;
+    const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
+    const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
+    const int moves = random_playout<row_t, BIG>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()]);
+    double r;
+    const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, area[b], max_h[b], has_buf != 0, bl, &r);
+    if (lane == 0) { outcome[idx] = e; score[idx] = r; moves_out[idx] = moves; }
+    if (board && lane < p.H) board[idx * p.H + lane] = (u64)myrow;
 }
 
 __global__ void k_fill_rank(DP p, double bl, int has_buf) {
@@ -4443,6 +4574,68 @@ extern "C" int rp_game_ended(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
     DISPATCH(ctx, k_game_ended, grid_for(B), d, (long long)B, drows, drem, dwh, darea, dmh, has ? 1 : 0, bl, dend, drew);
     HIPCHK(ctx, hipMemcpyAsync(ended_out, dend, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(reward_out, drew, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RP_OK;
+}
+
+#define RP_MAX_PLAYOUTS 256
+// k_rollout / k_rollout_states instance of the context's geometry (64-bit rows beyond W = 32, the second item word beyond N = 64)
+#define DISPATCH_ROLLOUT(ctx, kernel, grid, ...)                                                           \
+    do {                                                                                                   \
+        const dim3 grid_(grid), block_(64 * WAVES_PER_BLOCK);                                              \
+        if ((ctx)->row64) { if ((ctx)->d.N > 64) hipLaunchKernelGGL((kernel<u64, true>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); else hipLaunchKernelGGL((kernel<u64, false>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); } \
+        else { if ((ctx)->d.N > 64) hipLaunchKernelGGL((kernel<u32, true>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); else hipLaunchKernelGGL((kernel<u32, false>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); } \
+        hipError_t le_ = hipGetLastError();                                                                \
+        if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of %s failed: %s", #kernel, hipGetErrorString(le_)); \
+    } while (0)
+
+extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, float *v_dev, int64_t capacity_rows) {
+    if (!ctx || !v_dev || capacity_rows < 0) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: bad argument");
+    if (playouts < 1 || playouts > RP_MAX_PLAYOUTS) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: playouts %d outside 1..%d", playouts, RP_MAX_PLAYOUTS);
+    const DP &d = ctx->d;
+    long long rows = std::min<long long>(capacity_rows, d.G);
+    if (rows == 0) return RP_OK;
+    DISPATCH_ROLLOUT(ctx, k_rollout, (unsigned)rows, d, (int)playouts, pi_dev, v_dev, (long long)capacity_rows);
+    return RP_OK;
+}
+
+extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
+                                 const int32_t *total_area, const int32_t *max_h, const uint64_t *episode_id, const double *rewards,
+                                 int32_t n_rewards, double alpha, int32_t playouts, int32_t *outcome_out, double *score_out, int32_t *moves_out,
+                                 uint64_t *board_out) {
+    if (!ctx || B < 0 || !rows || !remaining || !item_wh || !total_area || !max_h || !outcome_out || !score_out || !moves_out || n_rewards < 0 ||
+        (n_rewards > 0 && !rewards))
+        return fail(ctx, RP_ERR_ARG, "rp_rollout_states: bad argument");
+    if (playouts < 1 || playouts > RP_MAX_PLAYOUTS) return fail(ctx, RP_ERR_ARG, "rp_rollout_states: playouts %d outside 1..%d", playouts, RP_MAX_PLAYOUTS);
+    if (B == 0) return RP_OK;
+    const DP &d = ctx->d;
+    const size_t n = (size_t)B * (size_t)playouts;
+    if (n > (size_t)0x7FFFFFFF) return fail(ctx, RP_ERR_ARG, "rp_rollout_states: %lld states x %d playouts exceed 2^31 - 1", (long long)B, playouts);
+    for (size_t k = 0; k < (size_t)B * d.N; ++k) {  // sizes outside the grid would shift by more than the row's width
+        const int w = item_wh[2 * k], h = item_wh[2 * k + 1];
+        if (w < 1 || w > d.W || h < 1 || h > d.H) return fail(ctx, RP_ERR_ARG, "rp_rollout_states: item %lld has size %dx%d outside the %dx%d grid", (long long)k, w, h, d.W, d.H);
+    }
+    double bl = 0.0;
+    bool has = rank_threshold(rewards, n_rewards, alpha, &bl);
+    Scratch s(ctx);
+    u64 *drows = s.up((const u64 *)rows, (size_t)B * d.H); NEED(drows);
+    u8 *drem = s.up(remaining, (size_t)B * d.N); NEED(drem);
+    u8 *dwh = s.up(item_wh, (size_t)B * d.N * 2); NEED(dwh);
+    int *darea = s.up(total_area, (size_t)B); NEED(darea);
+    int *dmh = s.up(max_h, (size_t)B); NEED(dmh);
+    u64 *dep = nullptr;
+    if (episode_id) { dep = s.up((const u64 *)episode_id, (size_t)B); NEED(dep); }
+    int *dout = s.up((const int *)nullptr, n); NEED(dout);
+    double *dscore = s.up((const double *)nullptr, n); NEED(dscore);
+    int *dmoves = s.up((const int *)nullptr, n); NEED(dmoves);
+    u64 *dboard = nullptr;
+    if (board_out) { dboard = s.up((const u64 *)nullptr, n * d.H); NEED(dboard); }
+    DISPATCH_ROLLOUT(ctx, k_rollout_states, (unsigned)grid_for((long long)n), d, (long long)B, (int)playouts, (const u64 *)drows, (const u8 *)drem,
+                     (const u8 *)dwh, (const int *)darea, (const int *)dmh, (const u64 *)dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
+    HIPCHK(ctx, hipMemcpyAsync(outcome_out, dout, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(score_out, dscore, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(moves_out, dmoves, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (board_out) HIPCHK(ctx, hipMemcpyAsync(board_out, dboard, n * d.H * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RP_OK;
 }

@@ -10,6 +10,9 @@ own engine context, HIP stream and captured HIP graph of one simulation WAVE:
     NNetWrapper.predict_from_stem   the rest of the CNN through PyTorch-ROCm (FP32)
     rp_commit_eval      mask / renormalise / expand / backup on device
 
+With evaluator="rollout" the two middle steps are one kernel, rp_rollout_eval: every waiting leaf's value is the mean outcome of
+`playouts` uniform random playouts and its prior is uniform -- plain MCTS with no network, the baseline a trained net is compared with.
+
 The groups' waves are launched alternately on their streams, so the latency-bound tree walk of one group runs while the
 CNN of the other occupies the matrix cores.  Moves are played on device (`RP_MOVE_SAMPLE` / `RP_MOVE_ARGMAX_FIRST` / `_DRAW`) and a
 finished slot immediately pulls the next instance of its group's pool, so the evaluator batch stays full until the pool
@@ -41,7 +44,13 @@ class _Group:
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         self.wide_logits = owner.wide_logits
-        if self.use_stem:  # the engine computes the first conv + pool itself: no plane tensor at all
+        self.rollout = owner.evaluator == "rollout"
+        self.playouts = owner.playouts
+        if self.rollout:  # no network: the uniform prior is written once, the playout kernel fills v every wave
+            self.planes = None
+            self.uniform_pi = torch.full((games, owner.A), float(np.float32(1) / np.float32(owner.A)), dtype=torch.float32, device=owner.device)
+            self.rollout_v = torch.zeros(games, dtype=torch.float32, device=owner.device)
+        elif self.use_stem:  # the engine computes the first conv + pool itself: no plane tensor at all
             self.channels_last = owner.channels_last
             self.resblock_kernel = owner.resblock_kernel
             fmt = torch.channels_last if self.channels_last else torch.contiguous_format
@@ -102,6 +111,10 @@ class _Group:
                 self.eng.commit_eval_host(pi, v)
             return
         self.eng.search_step(sync=False)
+        if self.rollout:
+            self.eng.rollout_eval(self.rollout_v.data_ptr(), self.G, self.playouts)
+            self.eng.commit_eval(self.uniform_pi.data_ptr(), self.rollout_v.data_ptr())
+            return
         self.leaf_inputs()
         self.pi, self.v = self.forward(nnet)
         self.commit(self.pi, self.v)
@@ -110,8 +123,12 @@ class _Group:
 class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
-                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True):
-        """wide_logits: action spaces beyond Engine.LOGITS_MAX_ACTIONS hand raw logits to rp_commit_eval_logits_wide (the softmax in the
+                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8):
+        """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
+        uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
+        or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
+        against rewards_list like every terminal: with an empty list every outcome is +1 and the search learns nothing from them.
+        wide_logits: action spaces beyond Engine.LOGITS_MAX_ACTIONS hand raw logits to rp_commit_eval_logits_wide (the softmax in the
         commit kernel, as on every smaller board); False keeps torch.softmax + rp_commit_eval for them (the A/B switch).
         record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
         return and the finished episodes' layouts are collected for pop_packings().
@@ -121,9 +138,20 @@ class BatchedSelfPlay:
         self.game, self.nnet, self.args = game, nnet, args
         self.W, self.H, self.N = game.bin_width, game.bin_height, game.num_items
         self.A = self.W * self.N
-        if nnet.device.type != "cuda":
-            raise RuntimeError("BatchedSelfPlay needs the evaluator on the GPU (args.cuda = True); there is no CPU path")
-        self.device = nnet.device if device is None else device
+        if evaluator not in ("cnn", "rollout"):
+            raise ValueError("evaluator must be 'cnn' or 'rollout', not %r" % (evaluator,))
+        self.evaluator, self.playouts = evaluator, int(playouts)
+        rollout = evaluator == "rollout"
+        if rollout:
+            if host_evaluator is not None:
+                raise ValueError("evaluator='rollout' evaluates the leaves on the device: it cannot be combined with host_evaluator")
+            if not 1 <= self.playouts <= _lib.Engine.MAX_PLAYOUTS:
+                raise ValueError("playouts must be in 1..%d, not %d" % (_lib.Engine.MAX_PLAYOUTS, self.playouts))
+            self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        else:
+            if nnet.device.type != "cuda":
+                raise RuntimeError("BatchedSelfPlay needs the evaluator on the GPU (args.cuda = True); there is no CPU path")
+            self.device = nnet.device if device is None else device
         groups = max(1, min(int(groups), int(games)))
         self.G = int(games)
         self.move_rule, self.node_cap, self.edge_cap, self.step_cap = move_rule, node_cap, edge_cap, int(step_cap)
@@ -136,12 +164,13 @@ class BatchedSelfPlay:
         self._packings = []
         self._pool_items = None
         self.use_graph = bool(use_graph) and host_evaluator is None
-        self.use_stem = bool(use_stem)
+        self.use_stem = bool(use_stem) and not rollout
         self.fuse_elementwise = bool(fuse_elementwise) and self.use_stem
         self.dense_small_convs = bool(dense_small_convs)
         self.channels_last = bool(channels_last) and self.fuse_elementwise
         self.resblock_kernel = bool(resblock_kernel) and self.channels_last
-        nnet.nnet.use_resblock_kernel = self.resblock_kernel
+        if not rollout:
+            nnet.nnet.use_resblock_kernel = self.resblock_kernel
         if self.channels_last:  # convolution weights in NHWC too, so MIOpen never converts per call
             nnet.nnet.to(memory_format=torch.channels_last)
         sizes = [self.G // groups + (1 if k < self.G % groups else 0) for k in range(groups)]
@@ -159,7 +188,7 @@ class BatchedSelfPlay:
     def close(self):
         for g in self.groups:
             g.graph = None
-            g.pi = g.v = g.stem = g.stem_relu = g.planes = None
+            g.pi = g.v = g.stem = g.stem_relu = g.planes = g.uniform_pi = g.rollout_v = None
             g.eng.close()
 
     @property
@@ -181,11 +210,12 @@ class BatchedSelfPlay:
             if g.graph is not None:
                 continue
             torch.cuda.synchronize(self.device)
-            with torch.cuda.stream(g.stream):
-                g.refresh_weights(self.nnet)
-                for _ in range(3):
-                    g.forward(self.nnet)
-            torch.cuda.synchronize(self.device)
+            if self.evaluator == "cnn":
+                with torch.cuda.stream(g.stream):
+                    g.refresh_weights(self.nnet)
+                    for _ in range(3):
+                        g.forward(self.nnet)
+                torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=g.stream):
                 g.wave_eager(self.nnet)
@@ -272,7 +302,7 @@ class BatchedSelfPlay:
             torch.cuda.synchronize(self.device)
         for g, (lo, hi) in zip(self.groups, self._blocks(self.n_instances)):
             wh_g = np.ascontiguousarray(item_wh[lo:hi]); area_g = np.ascontiguousarray(total_area[lo:hi])
-            if self.host_evaluator is None:
+            if self.host_evaluator is None and self.evaluator == "cnn":
                 with torch.cuda.stream(g.stream):
                     g.refresh_weights(self.nnet)  # stem tables follow in-place weight updates
             g.eng.set_rank_buffer(buf)
@@ -295,7 +325,7 @@ class BatchedSelfPlay:
             self.nnet.refresh_fused()
             torch.cuda.synchronize(self.device)
         for g, (lo, hi) in zip(self.groups, self._blocks(self.n_instances)):
-            if self.host_evaluator is None:
+            if self.host_evaluator is None and self.evaluator == "cnn":
                 with torch.cuda.stream(g.stream):
                     g.refresh_weights(self.nnet)
             g.eng.set_rank_buffer(buf)

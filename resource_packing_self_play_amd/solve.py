@@ -200,7 +200,10 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     buffer can choose other moves.
     games: concurrent slots (default min(n, 4096)); more instances than slots go through the engine's auto-restart.
     driver: a BatchedSelfPlay with record_packings=True to reuse (its move rule is set; it is left open); otherwise one is built
-    with **driver_kw, records no training examples (max_examples=0) and is closed afterwards."""
+    with **driver_kw, records no training examples (max_examples=0) and is closed afterwards.
+    Network-free: pack(game, None, args, evaluator="rollout", playouts=K, rewards_list=...) searches with uniform priors and the mean
+    outcome of K random playouts per leaf (BatchedSelfPlay's evaluator="rollout").  The playouts are ranked against rewards_list too: with
+    an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one."""
     from .selfplay import BatchedSelfPlay
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
@@ -216,3 +219,30 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     finally:
         if driver is None:
             sp.close()
+
+
+def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None):
+    """Scores of uniform random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin
+    (rp_rollout_states; instance i plays as episode i, playout j draws from (seed, i, j)).  The random baseline a search or a trained
+    network is compared with, and -- flattened -- a first R2 buffer for pack(..., evaluator="rollout", rewards_list=...).
+    item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them."""
+    if (item_wh is None) == (seeds is None):
+        raise ValueError("give either item_wh or seeds")
+    W, H, N = game.bin_width, game.bin_height, game.num_items
+    eng = _lib.Engine(W, H, N, 1, 1, seed=int(seed) & 0x7FFFFFFFFFFFFFFF)
+    try:
+        if seeds is not None:
+            item_wh = eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
+            area = np.full(len(item_wh), int(bin_w or W) * int(bin_h or H), np.int32)
+        else:
+            item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8).reshape(-1, N, 2)
+            area = (item_wh[:, :, 0].astype(np.int32) * item_wh[:, :, 1]).sum(axis=1).astype(np.int32)
+        n = len(item_wh)
+        if n == 0:
+            return np.zeros((0, int(playouts)), np.float64)
+        max_h = item_wh[:, :, 1].max(axis=1).astype(np.int32)
+        _, score, _, _ = eng.rollout_states(np.zeros((n, H), np.uint64), np.ones((n, N), np.uint8), item_wh, area, max_h, (), 0.75, playouts,
+                                            episode_id=np.arange(n, dtype=np.uint64), boards=False)
+        return score
+    finally:
+        eng.close()
