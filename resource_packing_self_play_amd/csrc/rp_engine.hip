@@ -3375,6 +3375,209 @@ __global__ void __launch_bounds__(256, 2) k_resstage32_pm(const float *__restric
     }
 }
 
+// Position-PAIRED variant of k_resstage16 for 10x10 images.  Sixteen leaves of a 10x10 image are 102 KB, one workgroup per
+// CU, so a tile here is TWO pixel positions with the same tap set, of EIGHT consecutive leaves each: B-operand lane n = (pair member
+// n >> 3, leaf n & 7), lane group g = channels 4 g .. 4 g + 3.  The image [position 100][leaf 8][16 floats] is 51 200 bytes (two
+// workgroups per CU), tiles are full and a tile's tap list is a compile-time property: 32 interior pairs x 9 taps, 16 edge pairs (both
+// members on the same edge) x 6 and the corner pairs TL + TR, BL + BR x 6 (the union of the two tap sets; the member a tap misses gets a
+// zero operand) -- 396 tile-taps per 8 leaves and convolution, 49.5 per leaf against 6 x 9 + 2.25 (tail blocks) = 56.25.  The 50 tiles
+// are dealt to the four waves so that every role issues 99 tile-taps (12 / 12 / 13 / 13 tiles: accumulators + skip operands in
+// registers); the four convolutions are a runtime loop.  Every output sums tap-major, then j = 0..3 on channels 4 g + j, from
+// rp_nn_pack_conv16's fragments -- k_resstage16<7>'s sums without the taps on padding: the same bits up to the sign of a zero.
+// Channel quad Q of (position p, leaf l) sits in slot Q ^ pp_swz(p, l), a function of the leaf and of the (row + column) parity, in which
+// the two members of every pair differ: the sixteen lanes of a ds_read_b128 lane group and the eight of a write group fall on different
+// bank quads, and the swizzle folds
+// into per-lane bases (one per pair distance and parity of member A's position): every LDS address is base + immediate.  One guard
+// position in front of and behind the image keeps the zeroed operands of the corner pairs (positions -1 and 100) inside the buffer.
+#define PP_LEAVES 8
+#define PP_POS_FLOATS (PP_LEAVES * 16)
+#define PP_LDS_BYTES ((size_t)(64 + 102 * PP_POS_FLOATS) * sizeof(float))  // [4][16] biases, guard + 100 positions + guard
+__host__ __device__ constexpr int pp_par(int p) { return ((p + 10) / 10 + (p + 10) % 10 + 1) & 1; }  // (row + column) & 1, defined for the guards too
+// slot swizzle of (position parity, leaf).  A ds_read_b128 is served in lane groups such as {0-3, 12-15, 20-27} (MI355X: sixteen 16-byte units
+// per cycle), which mix two channel groups g, both members and both leaf halves; the unit of a lane is 4 (leaf & 3) + slot.  A ds_write_b128
+// goes eight consecutive lanes at a time over eight units, 4 (leaf & 1) + slot.  3 (leaf >> 2) ^ (leaf >> 1 & 1) ^ 2 parity separates both.
+__host__ __device__ constexpr int pp_swz_par(int par, int leaf) { return (par << 1) ^ (3 * ((leaf >> 2) & 1)) ^ ((leaf >> 1) & 1); }
+__host__ __device__ constexpr int pp_swz(int p, int leaf) { return pp_swz_par(pp_par(p), leaf); }
+__host__ __device__ constexpr int pp_off(int p, int leaf, int quad) { return ((p + 1) * PP_LEAVES + leaf) * 16 + 4 * (quad ^ pp_swz(p, leaf)); }  // floats from the front guard
+__host__ __device__ constexpr int pp_tap_ok(int p, int tap) {  // tap's input pixel of position p lies inside the image
+    const int r = p / 10 + tap / 3 - 1, c = p % 10 + tap % 3 - 1;
+    return r >= 0 && r < 10 && c >= 0 && c < 10;
+}
+__host__ __device__ constexpr int pp_tap_mask(int p) {
+    int m = 0;
+    for (int tap = 0; tap < 9; ++tap) m |= pp_tap_ok(p, tap) << tap;
+    return m;
+}
+struct PpTile { int pa, d; };  // member A's position, member B's = pa + d (d = 1: row neighbours, 10: column neighbours, 9: the corners of a row)
+__host__ __device__ constexpr PpTile pp_tile(int t) {
+    if (t < 32) return {(1 + t / 4) * 10 + 1 + 2 * (t % 4), 1};  // interior
+    if (t < 36) return {1 + 2 * (t - 32), 1};                     // top edge
+    if (t < 40) return {90 + 1 + 2 * (t - 36), 1};                // bottom edge
+    if (t < 44) return {(1 + 2 * (t - 40)) * 10, 10};             // left edge
+    if (t < 48) return {(1 + 2 * (t - 44)) * 10 + 9, 10};         // right edge
+    return {t == 48 ? 0 : 90, 9};                                 // TL + TR, BL + BR
+}
+__host__ __device__ constexpr int pp_role_tile(int role, int i) {  // i-th tile of a wave role, -1 past its last: 9 + 3, 9 + 3, 7 + 6, 7 + 4 + 2
+    if (role == 0) return i < 9 ? i : i < 12 ? 32 + (i - 9) : -1;
+    if (role == 1) return i < 9 ? 9 + i : i < 12 ? 35 + (i - 9) : -1;
+    if (role == 2) return i < 7 ? 18 + i : i < 13 ? 38 + (i - 7) : -1;
+    return i < 7 ? 25 + i : i < 13 ? 44 + (i - 7) : -1;
+}
+__host__ __device__ constexpr int pp_dcls(int d) { return d == 1 ? 0 : d == 10 ? 1 : 2; }
+// a lane's LDS base (floats from the front guard) for pairs of distance d whose member A's accessed position has parity par_a; the
+// access of (member, leaf, quad g) at member A's position q is base + (q + 1) * PP_POS_FLOATS
+__host__ __device__ constexpr int pp_lane_base(int d, int par_a, int lane) {
+    const int n = lane & 15, g = lane >> 4, m = n >> 3, leaf = n & 7;
+    return (m * d * PP_LEAVES + leaf) * 16 + 4 * (g ^ pp_swz_par(par_a ^ m, leaf));  // the members of every pair differ in parity
+}
+struct PpList {  // a role's tiles and its (tap, own tile index k, member A's input position q and its parity, members to zero) in execution order
+    int n, np, ok;
+    int pa[13], d[13];
+    signed char s[100], k[100], q[100], par[100], za[100], zb[100];
+};
+constexpr PpList pp_make_list(int role) {
+    PpList L{};
+    while (L.np < 13 && pp_role_tile(role, L.np) >= 0) { const PpTile t = pp_tile(pp_role_tile(role, L.np)); L.pa[L.np] = t.pa; L.d[L.np] = t.d; ++L.np; }
+    L.ok = 1;
+    for (int s = 0; s < 9; ++s) {
+        int cnt = 0;
+        for (int k = 0; k < L.np; ++k) {
+            const int a = pp_tap_ok(L.pa[k], s), b = pp_tap_ok(L.pa[k] + L.d[k], s);
+            if (!a && !b) continue;
+            L.s[L.n] = (signed char)s; L.k[L.n] = (signed char)k; L.q[L.n] = (signed char)(L.pa[k] + (s / 3 - 1) * 10 + s % 3 - 1);
+            L.par[L.n] = (signed char)(pp_par(L.pa[k]) ^ ((s / 3 + s % 3) & 1));  // of the row and column before a corner's wrap-around
+            L.za[L.n] = (signed char)!a; L.zb[L.n] = (signed char)!b; ++L.n; ++cnt;
+        }
+        if (cnt == 0) L.ok = 0;  // the weight stream is advanced by a tap's first entry: every tap needs one
+    }
+    return L;
+}
+template <int ROLE> struct PpTab { static constexpr PpList L = pp_make_list(ROLE); };
+static_assert(PpTab<0>::L.n == 99 && PpTab<1>::L.n == 99 && PpTab<2>::L.n == 99 && PpTab<3>::L.n == 99 && PpTab<0>::L.ok && PpTab<1>::L.ok && PpTab<2>::L.ok && PpTab<3>::L.ok &&
+              PpTab<0>::L.np + PpTab<1>::L.np + PpTab<2>::L.np + PpTab<3>::L.np == 50, "10x10: 50 tiles, 99 tile-taps per wave role");
+template <int ROLE>
+__device__ __forceinline__ void pp_body(const float *__restrict__ x, const float *__restrict__ frag, float *__restrict__ out, float *__restrict__ out_relu, long long B,
+                                        long long leaf0, long long stride_leaves, const float *sbias, float *img) {
+    using T = PpTab<ROLE>;
+    constexpr int NP = T::L.np, NE = T::L.n, CONV_BYTES = 9 * 1024, LEAF_BYTES = 100 * 64;
+    const int lane = lane_id(), n = lane & 15, g = lane >> 4, mb = n >> 3;
+    float *lb[3][2];  // per pair distance and parity of member A's position; the ones a role does not use are never formed
+    int xo[3];        // byte offset of (leaf, member, channel quad g) in a task's x / out, + 64 * member A's position
+    pm_for<3>([&](auto C) {
+        constexpr int c = decltype(C)::value, d = c == 0 ? 1 : c == 1 ? 10 : 9;
+        lb[c][0] = img + pp_lane_base(d, 0, lane); lb[c][1] = img + pp_lane_base(d, 1, lane);
+        xo[c] = (n & 7) * LEAF_BYTES + mb * d * 64 + g * 16;
+    });
+    const int voff = lane * 16;
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)frag, 0, 4 * CONV_BYTES, RS_BUF_FLAGS);
+    f32x4 xs[NP], acc[NP], wq[3], bq[6];
+    wq[0] = rs_load_b(frs, voff, 0); wq[1] = rs_load_b(frs, voff, 1024);
+    auto b_read = [&](auto E) {  // operand of entry E: the tap's input position of this lane's member, leaf and channel group
+        constexpr int e = decltype(E)::value, q = T::L.q[e], c = pp_dcls(T::L.d[T::L.k[e]]);
+        return *(const f32x4 *)(lb[c][T::L.par[e]] + (q + 1) * PP_POS_FLOATS);
+    };
+    auto own = [&](auto K) -> float * {  // this lane's (member, leaf, quad g) of tile K in the image
+        constexpr int k = decltype(K)::value, p = T::L.pa[k];
+        return lb[pp_dcls(T::L.d[k])][pp_par(p)] + (p + 1) * PP_POS_FLOATS;
+    };
+    for (; leaf0 < B; leaf0 += stride_leaves) {
+        const int nbytes = (int)(B - leaf0 < PP_LEAVES ? B - leaf0 : PP_LEAVES) * LEAF_BYTES;  // leaves past B: loads return zeros, stores are dropped
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)leaf0 * 1600), 0, nbytes, RS_BUF_FLAGS);
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            xs[k] = rs_load_x(xrs, xo[pp_dcls(T::L.d[k])], T::L.pa[k] * 64);
+        });
+        pm_for<NP>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            *(f32x4 *)own(K) = rs_relu(xs[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        lds_barrier();
+#pragma unroll 1
+        for (int kc = 0; kc < 4; ++kc) {  // block 0 conv0, conv1 (+ skip x), block 1 conv0, conv1 (+ skip y1)
+            const int fbase = kc * CONV_BYTES, fnext = ((kc + 1) & 3) * CONV_BYTES;
+            pm_for<NP>([&](auto K) { acc[decltype(K)::value] = (f32x4){0.f, 0.f, 0.f, 0.f}; });
+            pm_for<4>([&](auto E) { bq[decltype(E)::value] = b_read(E); });
+            pm_for<(NE + 1) / 2>([&](auto P) {  // two entries (different tiles) at a time: two independent accumulator chains, operands four entries ahead
+                constexpr int e0 = 2 * decltype(P)::value, e1 = e0 + 1 < NE ? e0 + 1 : e0, s0 = T::L.s[e0], s1 = T::L.s[e1], k0 = T::L.k[e0], k1 = T::L.k[e1];
+                static_assert(e1 == e0 || k0 != k1, "a pair's entries belong to different tiles");
+                const f32x4 w0 = wq[s0 % 3];
+                if constexpr (e0 == 0 || T::L.s[e0 > 0 ? e0 - 1 : 0] != s0)  // first entry of tap s: request the fragment of tap s + 2
+                    wq[(s0 + 2) % 3] = rs_load_b(frs, voff, s0 + 2 < 9 ? fbase + (s0 + 2) * 1024 : fnext + (s0 + 2 - 9) * 1024);
+                if constexpr (s1 != s0)
+                    wq[(s1 + 2) % 3] = rs_load_b(frs, voff, s1 + 2 < 9 ? fbase + (s1 + 2) * 1024 : fnext + (s1 + 2 - 9) * 1024);
+                const f32x4 w1 = wq[s1 % 3];
+                f32x4 b0 = bq[e0 % 6], b1 = bq[e1 % 6];
+                if constexpr (e0 + 4 < NE) bq[(e0 + 4) % 6] = b_read(std::integral_constant<int, (e0 + 4 < NE ? e0 + 4 : 0)>{});
+                if constexpr (e0 + 5 < NE) bq[(e0 + 5) % 6] = b_read(std::integral_constant<int, (e0 + 5 < NE ? e0 + 5 : 0)>{});
+                // a corner pair's tap that only the other member has: this member multiplies zeros, as on padding
+                if constexpr (T::L.za[e0] || T::L.zb[e0]) b0 = (mb ? T::L.zb[e0] : T::L.za[e0]) ? (f32x4){0.f, 0.f, 0.f, 0.f} : b0;
+                if constexpr (T::L.za[e1] || T::L.zb[e1]) b1 = (mb ? T::L.zb[e1] : T::L.za[e1]) ? (f32x4){0.f, 0.f, 0.f, 0.f} : b1;
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[k0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[j], b0[j], acc[k0], 0, 0, 0);
+                    if constexpr (e1 != e0) acc[k1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[j], b1[j], acc[k1], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            lds_barrier();  // every wave has read the image: the results may overwrite it
+            const f32x4 ba = *(const f32x4 *)(sbias + 16 * kc + 4 * g);
+            if (kc < 3) {
+                if (kc == 1)  // y1 = conv + bias + x, kept as block 1's skip operand
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value;
+                        xs[k] = (acc[k] + ba) + xs[k];
+                        *(f32x4 *)own(K) = rs_relu(xs[k]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                else
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value;
+                        *(f32x4 *)own(K) = rs_relu(acc[k] + ba);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                lds_barrier();
+            } else {
+                const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)leaf0 * 1600), 0, nbytes, RS_BUF_FLAGS);
+                pm_for<NP>([&](auto K) {
+                    constexpr int k = decltype(K)::value;
+                    acc[k] = (acc[k] + ba) + xs[k];
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[k]), ors, xo[pp_dcls(T::L.d[k])], T::L.pa[k] * 64, RS_STREAM_AUX);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                if (out_relu != nullptr) {  // uniform: relu(result) for the next layer's input
+                    const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(out_relu + (size_t)leaf0 * 1600), 0, nbytes, RS_BUF_FLAGS);
+                    pm_for<NP>([&](auto K) {
+                        constexpr int k = decltype(K)::value;
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[k])), rrs, xo[pp_dcls(T::L.d[k])], T::L.pa[k] * 64, RS_STREAM_AUX);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                }
+            }
+        }
+    }
+}
+// A workgroup of four waves per task of eight leaves, persistent.  frag / bias as k_resstage16 (rp_nn_pack_conv16).
+__global__ void __launch_bounds__(256, 2) k_resstage16_pp(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
+                                                          float *__restrict__ out, float *__restrict__ out_relu, long long B, const int *__restrict__ nrows_dev) {
+    extern __shared__ __attribute__((aligned(16))) float rb_lds[];
+    const int wv = wave_in_block();
+    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    if ((long long)blockIdx.x * PP_LEAVES >= B) return;
+    float *sbias = rb_lds;  // [4][16]
+    for (int i = threadIdx.x; i < 64; i += blockDim.x) sbias[i] = bias[i];
+    __syncthreads();
+    const long long leaf0 = (long long)blockIdx.x * PP_LEAVES, stride = (long long)gridDim.x * PP_LEAVES;  // the same tasks for the four waves: uniform barriers
+    float *img = rb_lds + 64;
+    switch (wv) {
+        case 0: pp_body<0>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+        case 1: pp_body<1>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+        case 2: pp_body<2>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+        default: pp_body<3>(x, frag, out, out_relu, B, leaf0, stride, sbias, img); break;
+    }
+}
+
 // Position-major entry of a 32-channel stage on 5x5 images: the 3x3 convolution 32 -> 32 + bias + max_pool2d(3, 2, 1) -> 3x3 that
 // k_convpool32<5, 32> below computes pixel-major (three leaves per wave, 75 of 80 columns, all nine taps: 240 tile-taps per leaf).  Same
 // image, wave roles and instruction streams as k_resstage32_pm<5> (PmTab<5, ROLE>: 169 tile-taps per leaf), ONE convolution per task:
@@ -4048,6 +4251,18 @@ static bool convpool32_pm_cheaper(long long B, int imgw) {
     return pm_rounds_cost(B, 16, STAGE_WAVES / 4) * 43 < pm_rounds_cost(B, imgw, STAGE_WAVES) * nt * 9;
 }
 
+// k_resstage16 or k_resstage16_pp for a 10x10 launch of B rows, by the same measure: 99 tile-taps of every wave role per task of eight
+// leaves over STAGE_WAVES / 4 workgroups against imgw leaves in nt tiles x 9 taps (+ the tail blocks: 288 of a tile's 1 152 cycles per
+// tap, 9 / 4 tile-taps) per wave and round; compared in quarter tile-taps.  The measure describes the steady state of persistent
+// workgroups; a launch whose typical wave gives a workgroup a single task has none (its x loads, which this kernel does not prefetch,
+// and its stores are hidden only by the CU's other workgroup), so such batches (c2: 4 096 rows) keep the old kernel.
+static bool stage16_pp_cheaper(long long B, int imgw, int nt, int tail) {
+    if (B <= 0) return false;
+    const long long typical = std::max<long long>(1, (long long)(0.92 * (double)B));
+    if ((typical + PP_LEAVES - 1) / PP_LEAVES <= STAGE_WAVES / 4) return false;
+    return pm_rounds_cost(B, PP_LEAVES, STAGE_WAVES / 4) * (4 * 99) < pm_rounds_cost(B, imgw, STAGE_WAVES) * (4 * nt * 9 + (tail ? 9 : 0));
+}
+
 // Leaves per WORKGROUP for the _wg stage kernels.  A CU works through its workgroups' pixel tiles at a fixed rate, so a launch takes
 // (workgroups on the busiest CU) x (tile slots of a workgroup = waves x tiles per wave): few large groups fill their tiles best but
 // quantise badly over the CUs (1 024 leaves in groups of 3 = 342 workgroups = 2 rounds on 86 CUs, 1 on the rest).  Cost for all B rows
@@ -4061,12 +4276,13 @@ static long long wg_group_cost(long long B, int k, int tile_slots, int n_cu) {
 // What one stage launch looks like, from the shape, the device figures and the knobs alone (no rp_ctx, no environment, no HIP call):
 // the kernel family and its template arguments (nt tiles per wave, waves, input channels, tail blocks; k_resstage32_pm: nt = the S * S
 // pixel positions), the leaves per wave or workgroup, the wave_floats argument of the convpool kernels, LDS bytes, grid and block.
-enum { FAM_NONE, FAM_RS16, FAM_RS16_WG, FAM_RS32, FAM_RS32_WG, FAM_RS32_PM, FAM_CP, FAM_CP_WG, FAM_CP_PM };
+enum { FAM_NONE, FAM_RS16, FAM_RS16_WG, FAM_RS32, FAM_RS32_WG, FAM_RS32_PM, FAM_CP, FAM_CP_WG, FAM_CP_PM, FAM_RS16_PP };
 enum { PLAN_OK, PLAN_BAD_SHAPE, PLAN_NO_LDS };
 struct StagePlan { int family, nt, waves, cin, tail, imgw, wave_floats; size_t lds; unsigned grid, block; };
 struct StageDevice { int n_cu; size_t lds_per_cu; };
-// resident workgroups per CU; tail blocks on / off; position-major stage (pm) and 5x5 entry (cp_pm) kernels 0: never, 1: always, -1: where cheaper
-struct StageKnobs { int wgs, tail, pm, cp_pm; };
+// resident workgroups per CU; tail blocks on / off; position-major stage (pm), 5x5 entry (cp_pm) and position-paired 10x10 stage (pp)
+// kernels 0: never, 1: always, -1: where cheaper
+struct StageKnobs { int wgs, tail, pm, cp_pm, pp; };
 
 // persistent grid: the work items, at most the workgroups that are resident at once (wgs per CU, fewer where LDS holds fewer)
 static unsigned stage_grid(long long work, const StageDevice &dev, size_t lds, int wgs) {
@@ -4117,7 +4333,17 @@ static int plan_resstage16(StagePlan *p, long long B, int H, int W, const StageD
     int imgw_max = std::max(1, (16 * 8) / PIX);
     while (imgw_max > 1 && 4 * (imgw_max * img_bytes + RS_STRIDE * sizeof(float)) + 1024 > 78 * 1024) --imgw_max;
     const int imgw = pick_leaves_per_wave(B, PIX, imgw_max);
-    return plan_waves(p, B, PIX, imgw, (size_t)16 * ((imgw * PIX + 15) / 16) * sizeof(int) + 4 * (imgw * img_bytes + RS_STRIDE * sizeof(float)), dev, kn.wgs, kn.tail != 0);
+    const int rc = plan_waves(p, B, PIX, imgw, (size_t)16 * ((imgw * PIX + 15) / 16) * sizeof(int) + 4 * (imgw * img_bytes + RS_STRIDE * sizeof(float)), dev, kn.wgs, kn.tail != 0);
+    // position-paired kernel (k_resstage16_pp) on 10x10; a device whose LDS cannot hold its image keeps k_resstage16, and the cost
+    // rule counts two resident workgroups per CU
+    if (H == 10 && W == 10 && PP_LDS_BYTES <= dev.lds_per_cu && (kn.pp == 1 || (kn.pp != 0 && rc == PLAN_OK && 2 * PP_LDS_BYTES <= dev.lds_per_cu && stage16_pp_cheaper(B, p->imgw, p->nt, p->tail)))) {
+        *p = StagePlan{};
+        p->family = FAM_RS16_PP; p->cin = 16; p->nt = 50; p->waves = 4; p->imgw = PP_LEAVES; p->block = 256;
+        p->lds = PP_LDS_BYTES;
+        p->grid = stage_grid((B + PP_LEAVES - 1) / PP_LEAVES, dev, p->lds, kn.wgs);
+        return PLAN_OK;
+    }
+    return rc;
 }
 
 static int plan_convpool32(StagePlan *p, long long B, int Cin, int H, int W, const StageDevice &dev, const StageKnobs &kn) {
@@ -4178,12 +4404,13 @@ static int plan_resstage32(StagePlan *p, long long B, int H, int W, const StageD
 }
 
 // The environment knobs of the stage launchers, entry 0: rp_nn_resstage16, 1: rp_nn_convpool32, 2: rp_nn_resstage32.
-// The workgroup and tail knobs are read once per process, RP_STAGE32_PM and RP_CONVPOOL_PM at every call: one process can run both kernels.
+// The workgroup and tail knobs are read once per process, RP_STAGE32_PM, RP_CONVPOOL_PM and RP_STAGE16_PP at every call: one process can run both kernels.
 static StageKnobs stage_knobs(int entry) {
     auto env_int = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
     static const int wgs[3] = {env_int("RP_STAGE16_WGS", 2), env_int("RP_CONVPOOL_WGS", 2), env_int("RP_STAGE32_WGS", 2)};  // resident workgroups per CU
     static const int tail[3] = {env_int("RP_STAGE16_TAIL", 1), env_int("RP_CONVPOOL_TAIL", 1), 0};                           // 0: the tail pixels as a whole tile (A/B)
-    return StageKnobs{wgs[entry], tail[entry], entry == 2 ? env_int("RP_STAGE32_PM", -1) : -1, entry == 1 ? env_int("RP_CONVPOOL_PM", -1) : 0};
+    return StageKnobs{wgs[entry], tail[entry], entry == 2 ? env_int("RP_STAGE32_PM", -1) : -1, entry == 1 ? env_int("RP_CONVPOOL_PM", -1) : 0,
+                      entry == 0 ? env_int("RP_STAGE16_PP", -1) : 0};
 }
 
 // For the host-side tests of the plans, the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
@@ -4192,7 +4419,7 @@ extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_
                                    int32_t pm_force, int64_t *out) {
     StagePlan p{};
     const StageDevice dev{n_cu, (size_t)lds_per_cu};
-    const StageKnobs kn{wgs, tail, pm_force, 0};  // the recorded plans (tests/golden/stage_plans.json) are k_convpool32's: rp_debug_convpool_plan has the knob
+    const StageKnobs kn{wgs, tail, pm_force, 0, 0};  // the recorded plans (tests/golden/stage_plans.json) are k_convpool32's and k_resstage16's: rp_debug_convpool_plan and rp_debug_stage16_plan have the knobs
     const int rc = entry == 0 ? plan_resstage16(&p, B, H, W, dev, kn) : entry == 1 ? plan_convpool32(&p, B, Cin, H, W, dev, kn) : plan_resstage32(&p, B, H, W, dev, kn);
     if (rc != PLAN_OK) p = StagePlan{};
     const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
@@ -4202,7 +4429,7 @@ extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_
 extern "C" int rp_debug_convpool_plan(int32_t Cin, int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail, int32_t cp_pm,
                                       int64_t *out) {  // rp_debug_stage_plan's entry 1 with the RP_CONVPOOL_PM knob
     StagePlan p{};
-    const int rc = plan_convpool32(&p, B, Cin, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, cp_pm});
+    const int rc = plan_convpool32(&p, B, Cin, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, cp_pm, 0});
     if (rc != PLAN_OK) p = StagePlan{};
     const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
     std::copy(f, f + 10, out);
@@ -4210,9 +4437,39 @@ extern "C" int rp_debug_convpool_plan(int32_t Cin, int64_t B, int32_t H, int32_t
 }
 extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) {
     StagePlan p;
-    return plan_resstage32(&p, B, H, W, StageDevice{256, 160 * 1024}, StageKnobs{2, 0, -1, 0}) == PLAN_OK && p.family == FAM_RS32_PM;
+    return plan_resstage32(&p, B, H, W, StageDevice{256, 160 * 1024}, StageKnobs{2, 0, -1, 0, 0}) == PLAN_OK && p.family == FAM_RS32_PM;
 }
 extern "C" int rp_debug_stage32_pm_swz(int32_t n) { return pm_swz(n); }
+extern "C" int rp_debug_stage16_plan(int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail, int32_t pp,
+                                     int64_t *out) {  // rp_debug_stage_plan's entry 0 with the RP_STAGE16_PP knob
+    StagePlan p{};
+    const int rc = plan_resstage16(&p, B, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, 0, pp});
+    if (rc != PLAN_OK) p = StagePlan{};
+    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
+    std::copy(f, f + 10, out);
+    return rc;
+}
+// k_resstage16_pp's tables and addresses, from the functions the kernel uses.  Byte offsets count from the front guard of the image.
+extern "C" int rp_debug_stage16_pp_off(int32_t pos, int32_t leaf, int32_t quad) { return 4 * pp_off(pos, leaf, quad); }  // where (position, leaf, channel quad) is stored
+static PpList pp_list(int role) { return role == 0 ? PpTab<0>::L : role == 1 ? PpTab<1>::L : role == 2 ? PpTab<2>::L : PpTab<3>::L; }
+// out: tiles, entries, then per tile (position of member A, of member B), then per entry (tap, tile index, zeroed member A, B)
+extern "C" int rp_debug_stage16_pp_role(int32_t role, int32_t *out) {
+    if (role < 0 || role > 3 || !out) return -1;
+    const PpList L = pp_list(role);
+    int32_t *o = out;
+    *o++ = L.np; *o++ = L.n;
+    for (int k = 0; k < L.np; ++k) { *o++ = L.pa[k]; *o++ = L.pa[k] + L.d[k]; }
+    for (int e = 0; e < L.n; ++e) { *o++ = L.s[e]; *o++ = L.k[e]; *o++ = L.za[e]; *o++ = L.zb[e]; }
+    return (int)(o - out);
+}
+// the byte offset `lane` reads for entry e of a role (base + immediate, as pp_body's b_read), e = -1 - k: where it writes tile k's result
+extern "C" int rp_debug_stage16_pp_lane_off(int32_t role, int32_t e, int32_t lane) {
+    if (role < 0 || role > 3 || lane < 0 || lane > 63) return -1;
+    const PpList L = pp_list(role);
+    if (e >= L.n || -1 - e >= L.np) return -1;
+    const int k = e >= 0 ? L.k[e] : -1 - e, q = e >= 0 ? L.q[e] : L.pa[k];
+    return 4 * (pp_lane_base(L.d[k], e >= 0 ? L.par[e] : pp_par(q), lane) + (q + 1) * PP_POS_FLOATS);
+}
 
 // LDS of one wave of k_commit: n_leaves float64 block sums, min(A, TERM_CHUNK) float32 terms, ceil(A / 32) + 1 mask words and, for the
 // logits modes, the row's `row_floats` probabilities.
@@ -4706,6 +4963,13 @@ extern "C" int rp_set_compact_rows(rp_ctx *ctx, int32_t enable) {
     return RP_OK;
 }
 
+// For the tests of the stage kernels' row limit (not in include/rp_engine.h): the limit is read from the caller's device int, nullptr: none.
+extern "C" int rp_debug_set_nn_rows(rp_ctx *ctx, const int *rows_dev) {
+    if (!ctx) return RP_ERR_ARG;
+    ctx->nn_rows_dev = rows_dev;
+    return RP_OK;
+}
+
 extern "C" int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples) {
     if (!ctx || move_rule < RP_MOVE_EXTERNAL || move_rule > RP_MOVE_ARGMAX_DRAW) return fail(ctx, RP_ERR_ARG, "rp_set_move_rule: bad argument");
     ctx->d.move_rule = move_rule;
@@ -4931,6 +5195,7 @@ static const StageEntry<ConvPoolFn> CP_TABLE[] = {cp<6, 16, true>(), cp<1, 16>()
 static const StageEntry<ConvPoolPmFn> CP_PM_TABLE[] = {{25, 4, 32, 0, k_convpool32_pm}};
 static const StageEntry<StageFn> RS32_WG_TABLE[] = {rs32_wg<2, 4>(), rs32_wg<3, 4>(), rs32_wg<4, 4>(), rs32_wg<3, 8>(), rs32_wg<4, 8>()};
 static const StageEntry<StagePmFn> RS32_PM_TABLE[] = {rs32_pm<3>(), rs32_pm<5>()};
+static const StageEntry<StagePmFn> RS16_PP_TABLE[] = {{50, 4, 16, 0, k_resstage16_pp}};
 static const StageEntry<StageFn> RS32_TABLE[] = {rs32<1>(), rs32<2>(), rs32<3>(), rs32<4>(), rs32<5>()};
 
 // The plan's kernel from its family's table: LDS allowance, launch, launch error.  The arguments convert to the kernel's parameter types.
@@ -4960,6 +5225,7 @@ extern "C" int rp_nn_resstage16(rp_ctx *ctx, const float *x_dev, const float *fr
     const int rc = !ctx || !x_dev || !frag4_dev || !bias4_dev || !out_dev ? PLAN_BAD_SHAPE : plan_resstage16(&p, B, H, W, StageDevice{ctx->n_cu, ctx->lds_per_cu}, stage_knobs(0));
     if (rc != PLAN_OK) return plan_error(ctx, rc, what, "images of at most 640 pixels", H, W, p);
     if (B == 0) return RP_OK;
+    if (p.family == FAM_RS16_PP) return launch_stage(ctx, what, p, RS16_PP_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, ctx->nn_rows_dev);
     if (p.family == FAM_RS16_WG) return launch_stage(ctx, what, p, RS16_WG_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, ctx->nn_rows_dev);
     return launch_stage(ctx, what, p, RS16_TABLE, x_dev, frag4_dev, bias4_dev, out_dev, out_relu_dev, B, H, W, p.imgw, ctx->nn_rows_dev);
 }

@@ -25,6 +25,7 @@ def means(src, counter):
                 name = r.get("Kernel_Name", "")
                 for k in KERNELS:
                     if k in name:
+                        # k_resstage16_pp (no template arguments) is filed under "k_resstage16": one 16-channel stage kernel runs per wave
                         if "k_convpool32_pm" in name:  # no template arguments; "<pm>" keeps it apart and among bench.py's k_convpool32 candidates
                             k = "k_convpool32<pm>"
                         elif k in ("k_resstage32", "k_convpool32"):  # two instantiations per wave: keep them apart by template arguments
