@@ -167,6 +167,7 @@ class Engine:
         self.L = load()
         self.W, self.H, self.N, self.A, self.G, self.sims = int(W), int(H), int(N), int(W) * int(N), int(games), int(sims)
         self.move_rule = int(move_rule)
+        self.device = int(device)
         cfg = RpConfig(ABI_VERSION, W, H, N, games, sims, float(cpuct), float(alpha), node_cap, edge_cap, move_rule,
                        auto_restart, 1 if reclaim else 0, 0, seed, tie_salt, device, vis_cap, stream or None, max_examples, max_sparse)
         self.KW = self.H * (2 if self.W > 32 else 1) + (self.N + 31) // 32
@@ -320,6 +321,8 @@ class Engine:
     @staticmethod
     def _bchw(x):
         """(rows, channels, inner) such that element e has channel (e // inner) % channels in x's memory order."""
+        if x.dim() < 2:
+            raise ValueError("tensor must have a batch and a channel dimension")
         if x.dim() == 4 and not x.is_contiguous():
             import torch
             if not x.is_contiguous(memory_format=torch.channels_last):
@@ -327,7 +330,33 @@ class Engine:
             return x.shape[0] * x.shape[2] * x.shape[3], x.shape[1], 1
         if not x.is_contiguous():
             raise ValueError("tensor must be contiguous")
-        return x.shape[0], x.shape[1], x[0, 0].numel()
+        inner = 1
+        for n in x.shape[2:]:
+            inner *= int(n)
+        return x.shape[0], x.shape[1], inner
+
+    def _nn_check(self, what, x, others, vectors):
+        """The element-wise kernels index every tensor the way they index x: `others` ({name: (tensor, shape)}) must be float32 tensors
+        on this context's device of the given shape in x's memory order (NCHW-contiguous or channels-last; where the two coincide -- one
+        channel or a 1x1 image -- either), `vectors` ({name: (tensor, elements)}) contiguous float32 vectors there."""
+        import torch
+        orders = None
+        for name, (t, shape) in [("x", (x, tuple(x.shape)))] + list(others.items()):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device.index != self.device:
+                raise ValueError("%s: %s must be a float32 tensor on device %d" % (what, name, self.device))
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError("%s: %s has shape %s, expected %s" % (what, name, tuple(t.shape), tuple(shape)))
+            mine = {"nchw"} if t.is_contiguous() else set()
+            if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+                mine.add("nhwc")
+            orders = mine if orders is None else orders & mine
+            if not orders:
+                raise ValueError("%s: %s is not in x's memory order (all tensors NCHW-contiguous or all channels-last)" % (what, name))
+        for name, (t, n) in vectors.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device.index != self.device:
+                raise ValueError("%s: %s must be a float32 tensor on device %d" % (what, name, self.device))
+            if t.numel() != n or not t.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous tensor of %d elements, got shape %s" % (what, name, n, tuple(t.shape)))
 
     kernel_events = None  # measurement aid: a list -> (name, start event, end event) of every fused evaluator kernel launched
 
@@ -344,9 +373,12 @@ class Engine:
 
     def nn_value_head(self, z, weight, bias, out):
         """out[b] = tanh(z[b] . weight + bias): z contiguous float32 [B, K], weight [1, K] or [K], bias [1], out [B] or [B, 1]."""
+        if z.dim() != 2:
+            raise ValueError("nn_value_head: z must be [B, K]")
         B, K = z.shape
-        if not (z.is_contiguous() and weight.is_contiguous() and out.is_contiguous()):
-            raise ValueError("nn_value_head needs contiguous tensors")
+        self._nn_check("nn_value_head", z, {}, {"weight": (weight, K), "bias": (bias, 1), "out": (out, B)})
+        if B == 0:
+            return
         self._ck(self.L.rp_nn_value_head(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(bias.data_ptr()),
                                          C.c_void_p(out.data_ptr()), B, K))
 
@@ -395,19 +427,40 @@ class Engine:
             C.c_void_p(out_relu.data_ptr()) if out_relu is not None else None, B, H, W)))
 
     def nn_bias_relu(self, x, bias):
+        """x = relu(x + bias[c]) in place; x NCHW-contiguous or channels-last with a multiple of 4 elements."""
         B, Cc, inner = self._bchw(x)
+        self._nn_check("nn_bias_relu", x, {}, {"bias": (bias, x.shape[1])})
+        if x.numel() == 0:  # an empty tensor has no address to pass
+            return x
         self._ck(self.L.rp_nn_bias_relu(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), B, Cc, inner))
         return x
 
     def nn_bias_residual(self, x, bias, res, out, out_relu=None):
+        """out = (x + bias[c]) + res, out_relu = relu(out): all of x's shape and memory order, a multiple of 4 elements."""
         B, Cc, inner = self._bchw(x)
+        same = {"res": (res, x.shape), "out": (out, x.shape)}
+        if out_relu is not None:
+            same["out_relu"] = (out_relu, x.shape)
+        self._nn_check("nn_bias_residual", x, same, {"bias": (bias, x.shape[1])})
+        if x.numel() == 0:
+            return
         self._ck(self.L.rp_nn_bias_residual(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(res.data_ptr()),
                                             C.c_void_p(out.data_ptr()), C.c_void_p(out_relu.data_ptr()) if out_relu is not None else None,
                                             B, Cc, inner))
 
     def nn_bias_pool(self, x, bias, out, out_relu=None):
+        """out = max_pool2d(x + bias[c], 3, 2, 1) [B, C, (H+1)//2, (W+1)//2], out_relu = relu(out), in x's memory order."""
+        if x.dim() != 4:
+            raise ValueError("nn_bias_pool: x must be [B, C, H, W]")
         B, Cc, H, W = x.shape
         cl = self._bchw(x)[2] == 1 and H * W > 1
+        pooled = (B, Cc, (H + 1) // 2, (W + 1) // 2)
+        same = {"out": (out, pooled)}
+        if out_relu is not None:
+            same["out_relu"] = (out_relu, pooled)
+        self._nn_check("nn_bias_pool", x, same, {"bias": (bias, Cc)})
+        if x.numel() == 0:
+            return
         self._ck(self.L.rp_nn_bias_pool(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
                                         C.c_void_p(out_relu.data_ptr()) if out_relu is not None else None, B, Cc, H, W, 1 if cl else 0))
 

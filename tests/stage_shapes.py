@@ -30,3 +30,27 @@ CONVPOOL32 = [(16, 5, 10, 10), (16, 1030, 10, 10), (16, 6, 9, 11), (16, 5, 7, 14
 # position-major rp_nn_resstage32 (RP_STAGE32_PM forced on and off), S x S images: batches per S
 # short last task, exactly one task, one leaf into the next task, more tasks than one round of a small grid
 STAGE32_PM_BATCHES = {3: (1, 15, 16, 17, 33, 1030), 5: (1, 15, 16, 17, 65, 1030)}
+
+# position-major rp_nn_convpool32 (RP_CONVPOOL_PM forced on and off), 32 -> 32 channels on 5x5: short task, one leaf short of a task,
+# exactly one, one into the next, a short last task, two tiles per wave of the pixel-major kernel
+CONVPOOL32_PM_BATCHES = (1, 15, 16, 17, 65, 1030)
+# position-paired rp_nn_resstage16 (RP_STAGE16_PP forced on and off) on 10x10: tasks of eight leaves; the last batch gives a workgroup
+# of a 256-CU device a second task (stage16_pp_worker.BATCHES)
+STAGE16_PP_BATCHES = (1, 7, 8, 9, 23, 8 * 512 + 3)
+
+ENTRY_RESSTAGE16, ENTRY_CONVPOOL32, ENTRY_RESSTAGE32 = 0, 1, 2  # rp_debug_stage_plan's entry
+KNOB_OF_ENTRY = ("RP_STAGE16_PP", "RP_CONVPOOL_PM", "RP_STAGE32_PM")  # read at every call: 0 = the pixel-major kernel, 1 = the newer one
+
+
+def row_limit_cases():
+    """The launches of test_gpu_stage_rows.py: (entry, Cin, B, H, W, knob) with every shape above under knob 0 and, where the newer
+    family takes the image size (10x10 at 16 channels, 5x5 at 32 -> 32, 3x3 and 5x5 at the 32-channel stages), under knob 1 as well.
+    test_stage_plans_host.py checks that they reach every kernel instantiation."""
+    cases = []
+    for (B, H, W) in RESSTAGE16 + [(B, 10, 10) for B in STAGE16_PP_BATCHES]:
+        cases += [(ENTRY_RESSTAGE16, 16, B, H, W, k) for k in ((0, 1) if (H, W) == (10, 10) else (0,))]
+    for (cin, B, H, W) in CONVPOOL32 + [(32, B, 5, 5) for B in CONVPOOL32_PM_BATCHES]:
+        cases += [(ENTRY_CONVPOOL32, cin, B, H, W, k) for k in ((0, 1) if (cin, H, W) == (32, 5, 5) else (0,))]
+    for (B, H, W) in RESSTAGE32 + [(B, S, S) for S, batches in STAGE32_PM_BATCHES.items() for B in batches]:
+        cases += [(ENTRY_RESSTAGE32, 32, B, H, W, k) for k in ((0, 1) if (H, W) in ((3, 3), (5, 5)) else (0,))]
+    return list(dict.fromkeys(cases))

@@ -91,3 +91,34 @@ def test_gpu_test_shapes_reach_every_entry_of_every_launch_table(golden, plan):
     assert len(TABLES) == 51 and len(set(TABLES)) == 51
     assert reached == set(TABLES), "never launched: %r; not in a table: %r" % (sorted(set(TABLES) - reached), sorted(reached - set(TABLES)))
 
+
+
+def test_row_limit_cases_reach_every_kernel_family_and_instantiation(golden):
+    """test_gpu_stage_rows.py pins the device row limit, the write bounds and the isolation of leaves per launch; every instantiation
+    handles the last, partly filled group of leaves in its own code, so its cases (stage_shapes.row_limit_cases) must reach every entry of
+    every launch table and the two families behind their own plan exports (k_resstage16_pp, k_convpool32_pm) -- each through the export
+    that has its entry point's per-call knob."""
+    import torch  # noqa: F401
+    L = ctypes.CDLL(LIB)
+    i32, i64, out_t = ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)
+    L.rp_debug_stage_plan.argtypes = [i32, i32, i64, i32, i32, i32, i64, i32, i32, i32, out_t]
+    L.rp_debug_convpool_plan.argtypes = [i32, i64, i32, i32, i32, i64, i32, i32, i32, out_t]
+    L.rp_debug_stage16_plan.argtypes = [i64, i32, i32, i32, i64, i32, i32, i32, out_t]
+    n_cu, lds = golden["devices"][0]["n_cu"], golden["devices"][0]["lds_per_cu"]
+    fam = golden["families"] + ["k_convpool32_pm", "k_resstage16_pp"]  # appended behind the recorded families (FAM_CP_PM, FAM_RS16_PP)
+    cases = stage_shapes.row_limit_cases()
+    assert len(cases) == len(set(cases))
+    reached = set()
+    for (entry, cin, B, H, W, knob) in cases:
+        out = (ctypes.c_int64 * 10)()
+        if entry == stage_shapes.ENTRY_RESSTAGE16:
+            rc = L.rp_debug_stage16_plan(B, H, W, n_cu, lds, 2, 1, knob, out)
+        elif entry == stage_shapes.ENTRY_CONVPOOL32:
+            rc = L.rp_debug_convpool_plan(cin, B, H, W, n_cu, lds, 2, 1, knob, out)
+        else:
+            rc = L.rp_debug_stage_plan(entry, cin, B, H, W, n_cu, lds, 2, 1, knob, out)
+        assert rc == 0 and out[5] >= 1, (entry, cin, B, H, W, knob)
+        reached.add((fam[out[0]],) + tuple(out[1:5]))
+    want = set(TABLES) | {("k_convpool32_pm", 25, 4, 32, 0), ("k_resstage16_pp", 50, 4, 16, 0)}
+    assert len(want) == 53
+    assert reached == want, "never launched: %r; not in a table: %r" % (sorted(want - reached), sorted(reached - want))
