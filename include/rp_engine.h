@@ -33,11 +33,12 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 8  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+#define RP_ABI_VERSION 9  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
                              5: placement trace (rp_set_trace, rp_pop_finished_packings)
                              6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan)
                              7: the commit kernel's softmax as a self-test (rp_selftest_softmax)
-                             8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states) */
+                             8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states)
+                             9: initial states of pool instances (rp_set_instance_initial) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -143,6 +144,18 @@ int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, const uint32_t 
  * array may be NULL (that field keeps its default); n must equal the pool's size.  The next rp_set_instance_pool* clears it.  The
  * metadata lives in device memory, so captured graphs stay valid. */
 int rp_set_instance_meta(rp_ctx *ctx, int64_t n, const uint64_t *episode_id /*[n]*/, const double *bl /*[n]*/, const uint8_t *has_buf /*[n]*/);
+/* Optional initial state of every instance of the pool set last by rp_set_instance_pool*: instance i starts at
+ * (rows[i], remaining[i]) instead of the empty bin with all N items (CoachBPP.py:67-68).  remaining[i][k] == 0: item k does not
+ * take part (its plane is zero from the first state on, BinPackingGame.py:86); its item_wh bytes are ignored.  max_h NULL:
+ * max_h[i] = largest h among the items with remaining != 0 (getInitItems, BinPackingGame.py:48, over the items that take part; 0
+ * if none); otherwise the caller's value (continuing an episode whose placed items count).  total_area stays what the pool was
+ * given: the caller includes the cells already set.  Moves are numbered from 0 at the initial state (sampling streams, trace,
+ * examples).  An instance whose initial state has no legal move is an episode of 0 moves: outcome and score are getGameEnded of
+ * that state (tie drawn as for Es), it gets a finished record (final bin = initial rows) and the slot takes the next instance.
+ * n must equal the pool's size; a row with a bit at or above W -> RP_ERR_ARG.  rows and remaining both NULL clears it; the next
+ * rp_set_instance_pool* clears it.  Device memory: captured graphs stay valid. */
+int rp_set_instance_initial(rp_ctx *ctx, int64_t n, const uint64_t *rows /*[n][H]*/, const uint8_t *remaining /*[n][N]*/,
+                            const int32_t *max_h /*[n] or NULL*/);
 /* R2 buffer snapshot (rewards_list argument of MCTS.getActionProb / getGameEnded, CoachBPP.py:76-91):
  * the threshold sorted[int(floor(len*alpha))-1] is recomputed and used by every slot from now on. */
 int rp_set_rank_buffer(rp_ctx *ctx, const double *rewards, int32_t n);

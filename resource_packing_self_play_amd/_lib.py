@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -54,6 +54,7 @@ _SIGS = {
     "rp_generate_items": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "rp_set_instance_pool_seeds": (C.c_int, [_vp, _i64, _vp, _i32, _i32, C.c_uint64]),
     "rp_set_instance_meta": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "rp_set_instance_initial": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "rp_set_rank_buffer": (C.c_int, [_vp, _vp, _i32]),
     "rp_set_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_set_stream": (C.c_int, [_vp, _vp]),
@@ -264,6 +265,20 @@ class Engine:
         bl = None if bl is None else _arr(bl, np.float64, (n,))
         has = None if has_buf is None else _arr(np.asarray(has_buf) != 0, np.uint8, (n,))
         self._ck(self.L.rp_set_instance_meta(self.h, n, _ptr(ids), _ptr(bl), _ptr(has)))
+
+    def set_instance_initial(self, rows=None, remaining=None, max_h=None):
+        """Initial states of the pool set last (rp_set_instance_initial): instance i starts at (rows[i] uint64 [H], remaining[i] uint8 [N])
+        instead of the empty bin with all items; max_h int32 [n] overrides the largest h of the items that take part.  rows and
+        remaining both None clears them."""
+        n = self.pool_size
+        if rows is None and remaining is None:
+            self._ck(self.L.rp_set_instance_initial(self.h, n, None, None, None))
+            return
+        if rows is None or remaining is None:
+            raise ValueError("rows and remaining go together")
+        rows = _arr(rows, np.uint64, (n, self.H)); remaining = _arr(np.asarray(remaining) != 0, np.uint8, (n, self.N))
+        mh = None if max_h is None else _arr(max_h, np.int32, (n,))
+        self._ck(self.L.rp_set_instance_initial(self.h, n, _ptr(rows), _ptr(remaining), _ptr(mh)))
 
     def set_roots(self, rows, remaining, first=0):
         rows = _arr(rows, np.uint64); count = rows.shape[0]

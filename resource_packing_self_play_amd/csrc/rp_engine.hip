@@ -82,6 +82,12 @@ struct PoolDesc {
     const unsigned long long *episode_id;
     const double *bl;
     const unsigned char *has_buf;
+    // optional per-instance initial state (rp_set_instance_initial), NULL = the empty bin with all N items: H row masks, the remaining
+    // items packed into the two 64-bit words of a key, and the episode's max_h (the caller's, or the largest h of the items that
+    // take part).  All three are set or none is.
+    const unsigned long long *init_rows;  // [n_instances][H]
+    const unsigned long long *init_rem;   // [n_instances][2]
+    const int *init_max_h;                // [n_instances]
 };
 // A visited edge: one 32-byte record = two 16-byte loads.  (Five parallel arrays -- idx, N, child, Q, P -- cost a node with a few visited
 // edges five cache lines per selection and a backup two; the record costs one.)
@@ -966,11 +972,67 @@ template <typename row_t, bool BIG = true> struct Tree {
 
 __device__ u64 sample_u64(u64 seed, u64 episode, u64 move) { return mix64(mix64(mix64(seed) ^ episode) ^ move); }
 
+// How a slot's episode ended, wave-uniform: term = Es of the state `node` it ended at (0: it has not ended), after `moves` moves, the
+// last of which was (action, filled) -- play_move_impl's registers; an initial state without a legal move ends its episode after 0 moves
+// (restart_slot_impl).
+struct EpisodeEnd {
+    int term, moves, action;
+    u32 node;
+    u64 filled;
+};
+
+// The finished record of slot g's episode: the score, the examples' values, the ring entry and -- under the trace -- the episode's moves
+// and final bin at the ring index of its record.  The last move comes from `e`, the earlier ones from the slot's running trace;
+// moves == 0 leaves a record without moves whose final bin is the initial state.  Leaves phase EPISODE_DONE.  The one copy of this code
+// in a kernel: play_move_impl and restart_slot_impl only report the end.
+template <typename row_t, bool BIG>
+__device__ void finish_episode_impl(const DP &p, Tree<row_t, BIG> &t, int g, const EpisodeEnd &e) {
+    const int lane = lane_id();
+    const u32 node = e.node;
+    const int term = e.term, moves = e.moves, last_action = e.action;
+    const u64 last_filled = e.filled;
+    row_t myrow; u64 rem0, rem1;
+    t.load_key(node, myrow, rem0, rem1);
+    double r;
+    ranked_reward<row_t>(myrow, p.H, p.W, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r);
+    t.count(CNT_EPISODES);
+    if (p.max_examples > 0)  // return [(x[0], x[1], r) for x in trainExamples] (CoachBPP.py:99)
+        for (int q = lane; q < moves && q < p.N; q += 64) {
+            u32 idx = p.slot_ex[(size_t)g * p.N + q];
+            if ((long long)idx < p.max_examples) p.ex_value[idx] = term;
+        }
+    int idx = 0;
+    if (lane == 0) {
+        p.last_outcome[g] = term;
+        p.last_score[g] = r;
+        p.phase[g] = RP_PHASE_EPISODE_DONE;
+        idx = atomicAdd(p.fin_count, 1);
+        if (idx < p.fin_cap) {
+            p.fin_episode[idx] = p.episode[g]; p.fin_outcome[idx] = term; p.fin_score[idx] = r; p.fin_moves[idx] = moves;
+        } else {
+            set_error(p, ERR_FINISHED_CAP);
+        }
+    }
+    if (p.tr_action) {  // the episode's trace and final bin, at the ring index of its record
+        idx = __shfl(idx, 0);
+        if (idx < p.fin_cap) {
+            for (int q = lane; q < p.N; q += 64) {  // earlier moves were stored by earlier launches (a launch plays one move per slot)
+                const bool earlier = q < moves - 1, last = q == moves - 1;
+                p.fin_tr_action[(size_t)idx * p.N + q] = last ? (u16)last_action : earlier ? p.tr_action[(size_t)g * p.N + q] : (u16)0;
+                p.fin_tr_rows[(size_t)idx * p.N + q] = last ? last_filled : earlier ? p.tr_rows[(size_t)g * p.N + q] : 0ull;
+            }
+            if (lane < p.H) p.fin_board[(size_t)idx * p.H + lane] = (u64)myrow;
+        }
+    }
+}
+
 // CoachBPP.executeEpisode's move (CoachBPP.py:86-99) for one slot whose search budget is spent.
-// action < 0: pick by p.move_rule.  Leaves phase RUNNING, EPISODE_DONE or FAILED.  DRAW = false (k_advance, which always passes an
+// action < 0: pick by p.move_rule.  Leaves phase RUNNING or FAILED, or reports the episode's end (the caller writes its record:
+// finish_episode_impl).  DRAW = false (k_advance, which always passes an
 // action) leaves the RP_MOVE_ARGMAX_DRAW branch out of the kernel.
 template <typename row_t, bool BIG, bool DRAW = true>
-__device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root, int action) {
+__device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root, int action) {
+    const EpisodeEnd none = {0, 0, 0, NONE32, 0ull};
     root = uni(root);
     NodeHdr hd = t.load_hdr(root);
     const int lane = lane_id();
@@ -1051,7 +1113,7 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
     }
     if (chosen == NONE32 && free_action < 0) {
         if (lane == 0) { set_error(p, ERR_BAD_ACTION); p.phase[g] = RP_PHASE_FAILED; }
-        return;
+        return none;
     }
     wave_sync();
     const int chosen_action = chosen != NONE32 ? (int)t.pAct[hd.prior_off + t.vis[chosen].idx] : free_action;
@@ -1060,7 +1122,7 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
         bool was_new;
         child = t.resolve_child(root, chosen, chosen_action, &was_new);
         wave_sync();
-        if (child == NONE32) { if (lane == 0) p.phase[g] = RP_PHASE_FAILED; return; }
+        if (child == NONE32) { if (lane == 0) p.phase[g] = RP_PHASE_FAILED; return none; }
     }
     if (p.max_examples > 0) {  // trainExamples.append([state, pi, None]) (CoachBPP.py:80)
         unsigned long long idx = 0, sp = 0;
@@ -1110,51 +1172,24 @@ __device__ void play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &roo
     NodeHdr ch = t.hdr[child];
     int moves = p.moves[g] + 1;
     if (lane == 0) { p.root[g] = root; p.moves[g] = moves; p.sims_done[g] = 0; }
-    if (ch.term != 0) {  // getGameEnded(next_state) != 0 (CoachBPP.py:91-99)
-        row_t myrow; u64 rem0, rem1;
-        t.load_key(child, myrow, rem0, rem1);
-        double r;
-        ranked_reward<row_t>(myrow, p.H, p.W, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r);
-        t.count(CNT_EPISODES);
-        if (p.max_examples > 0)  // return [(x[0], x[1], r) for x in trainExamples] (CoachBPP.py:99)
-            for (int q = lane; q < moves && q < p.N; q += 64) {
-                u32 idx = p.slot_ex[(size_t)g * p.N + q];
-                if ((long long)idx < p.max_examples) p.ex_value[idx] = ch.term;
-            }
-        int idx = 0;
-        if (lane == 0) {
-            p.last_outcome[g] = ch.term;
-            p.last_score[g] = r;
-            p.phase[g] = RP_PHASE_EPISODE_DONE;
-            idx = atomicAdd(p.fin_count, 1);
-            if (idx < p.fin_cap) {
-                p.fin_episode[idx] = p.episode[g]; p.fin_outcome[idx] = ch.term; p.fin_score[idx] = r; p.fin_moves[idx] = moves;
-            } else {
-                set_error(p, ERR_FINISHED_CAP);
-            }
-        }
-        if (p.tr_action) {  // the episode's trace and final bin, at the ring index of its record
-            idx = __shfl(idx, 0);
-            if (idx < p.fin_cap) {
-                for (int q = lane; q < p.N; q += 64) {  // earlier moves were stored by earlier launches (a launch plays one move per slot)
-                    const bool earlier = q < moves - 1, last = q == moves - 1;
-                    p.fin_tr_action[(size_t)idx * p.N + q] = last ? (u16)chosen_action : earlier ? p.tr_action[(size_t)g * p.N + q] : (u16)0;
-                    p.fin_tr_rows[(size_t)idx * p.N + q] = last ? filled : earlier ? p.tr_rows[(size_t)g * p.N + q] : 0ull;
-                }
-                if (lane < p.H) p.fin_board[(size_t)idx * p.H + lane] = (u64)myrow;
-            }
-        }
-    } else if (lane == 0) {
+    if (ch.term != 0)  // getGameEnded(next_state) != 0 (CoachBPP.py:91-99)
+        return EpisodeEnd{(int)ch.term, moves, chosen_action, child, filled};
+    if (lane == 0) {
         p.last_outcome[g] = 0;
         p.last_score[g] = 0.0;
         p.phase[g] = RP_PHASE_RUNNING;
     }
+    return none;
 }
 
 // A slot whose episode ended takes the next instance of the pool (CoachBPP.py:123-134: the next self-play
 // episode, a new MCTS with an empty tree).  Leaves the slot RUNNING at the new root, or IDLE when the pool is used up.
+// The root is the empty bin with all N items (CoachBPP.py:67-68) or the instance's initial state (rp_set_instance_initial).  An initial
+// state without a legal move is an episode of 0 moves: it is reported as ended (the caller writes its record and restarts again), so
+// a terminal root never reaches k_search or the move routine.
 template <typename row_t, bool BIG>
-__device__ void restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root) {
+__device__ EpisodeEnd restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root) {
+    const EpisodeEnd none = {0, 0, 0, NONE32, 0ull};
     const int lane = lane_id();
     unsigned long long idx = 0;
     if (lane == 0) idx = atomicAdd(p.next_instance, 1ull);
@@ -1162,14 +1197,14 @@ __device__ void restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &
     const PoolDesc pd = *p.pool_desc;
     if ((long long)idx >= pd.n_instances) {
         if (lane == 0) p.phase[g] = RP_PHASE_IDLE;
-        return;
+        return none;
     }
     u8 *wh = p.item_wh + (size_t)g * p.N * 2;
     const u8 *src = pd.wh + (size_t)idx * p.N * 2;
     for (int q = lane; q < 2 * p.N; q += 64) wh[q] = src[q];
     for (int s = lane; s < p.table_cap; s += 64) t.table[s] = 0ull;
     if (lane == 0) {
-        p.total_area[g] = pd.area[idx]; p.max_h[g] = pd.max_h[idx];
+        p.total_area[g] = pd.area[idx]; p.max_h[g] = pd.init_rows ? pd.init_max_h[idx] : pd.max_h[idx];
         p.episode[g] = pd.episode_id ? pd.episode_id[idx] : pd.first_id + idx; p.moves[g] = 0; p.sims_done[g] = 0;
         p.bl[g] = pd.bl ? pd.bl[idx] : *p.g_bl; p.has_buf[g] = pd.has_buf ? (int)pd.has_buf[idx] : *p.g_has_buf;
         p.last_outcome[g] = 0; p.last_score[g] = 0.0;
@@ -1180,9 +1215,33 @@ __device__ void restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &
     bool was_new;
     row_t myrow = 0;
     u64 rem0 = full_mask(p.N > 64 ? 64 : p.N), rem1 = p.N > 64 ? full_mask(p.N - 64) : 0ull;
+    if (pd.init_rows) {
+        if (lane < p.H) myrow = (row_t)pd.init_rows[(size_t)idx * p.H + lane];
+        rem0 = uni(pd.init_rem[2 * idx]);
+        rem1 = p.N > 64 ? uni(pd.init_rem[2 * idx + 1]) : 0ull;
+    }
     root = t.find_or_materialize(myrow, rem0, rem1, &was_new);
     wave_sync();
     if (lane == 0) { p.root[g] = root; p.phase[g] = root == NONE32 ? RP_PHASE_FAILED : RP_PHASE_RUNNING; }
+    if (root == NONE32) return none;
+    return EpisodeEnd{uni((int)t.hdr[root].term), 0, 0, root, 0ull};  // getGameEnded(initial state) != 0: nothing to search
+}
+
+// Writes the record of an episode that has ended and, under auto_restart, gives the slot the next instance of the pool -- again while
+// that instance ends before its first move (an initial state without a legal move); without initial states a restart always finds a
+// live root.  BEGIN: the slot starts the pool (k_pool_begin: no episode precedes the first instance).
+template <bool BEGIN, typename row_t, bool BIG>
+__device__ void finish_and_restart(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root, EpisodeEnd e) {
+    for (bool first = BEGIN;; first = false) {
+        if (!first) {
+            if (e.term == 0) return;
+            finish_episode_impl<row_t>(p, t, g, e);
+            wave_sync();
+            if (!p.auto_restart) return;
+        }
+        e = restart_slot_impl<row_t>(p, t, g, root);
+        wave_sync();
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1297,12 +1356,9 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_moves(DP p) {
     __shared__ u32 s_vmask[WAVES_PER_BLOCK][MAX_MASK_WORDS];
     Tree<row_t> t(p, g, s_stage + (size_t)wave_in_block() * p.A, s_vm[wave_in_block()], s_vmask[wave_in_block()]);
     u32 root = p.root[g];
-    play_move_impl<row_t>(p, t, g, root, -1);
+    const EpisodeEnd e = play_move_impl<row_t>(p, t, g, root, -1);
     wave_sync();
-    if (p.phase[g] == RP_PHASE_EPISODE_DONE && p.auto_restart) {
-        restart_slot_impl<row_t>(p, t, g, root);
-        wave_sync();
-    }
+    finish_and_restart<false, row_t>(p, t, g, root, e);
     t.store_sizes();
     t.flush_counters();
 }
@@ -1964,7 +2020,8 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_advance(DP p, int firs
     __shared__ u32 s_vmask[WAVES_PER_BLOCK][MAX_MASK_WORDS];
     Tree<row_t> t(p, g, s_stage + (size_t)wave_in_block() * p.A, s_vm[wave_in_block()], s_vmask[wave_in_block()]);
     u32 root = p.root[g];
-    play_move_impl<row_t, true, false>(p, t, g, root, action[k]);
+    const EpisodeEnd e = play_move_impl<row_t, true, false>(p, t, g, root, action[k]);
+    if (e.term != 0) finish_episode_impl<row_t>(p, t, g, e);
     t.store_sizes();
     t.flush_counters();
 }
@@ -1993,7 +2050,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_pool_begin(DP p) {
     __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
     Tree<row_t> t(p, g, s_stage + (size_t)wave_in_block() * p.A, s_vm[wave_in_block()]);
     u32 root = NONE32;
-    restart_slot_impl<row_t>(p, t, g, root);
+    finish_and_restart<true, row_t>(p, t, g, root, EpisodeEnd{0, 0, 0, NONE32, 0ull});
     t.store_sizes();
     t.flush_counters();
 }
@@ -4152,6 +4209,10 @@ struct rp_ctx {
     double *meta_bl;
     u8 *meta_has;
     int64_t meta_cap;
+    u64 *init_rows = nullptr, *init_rem = nullptr;  // rp_set_instance_initial's arrays (capacity init_cap)
+    int *init_max_h = nullptr;
+    int64_t init_cap = 0;
+    PoolDesc pd = {};   // host copy of *d.pool_desc: the pool, its metadata and its initial states are set by separate calls
     int n_cu = 256;                   // compute units and LDS bytes per CU of the device (hipDeviceProp, read once in rp_create)
     size_t lds_per_cu = 160 * 1024;
     int compact_rows = 0;             // rp_set_compact_rows: rp_search_step(ctx, NULL) lists the waiting slots on the device too
@@ -5448,8 +5509,8 @@ extern "C" int rp_set_instance_pool(rp_ctx *ctx, int64_t n_instances, const uint
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     d.pool_wh = ctx->pool_wh; d.pool_area = ctx->pool_area; d.pool_max_h = ctx->pool_max_h;
     d.n_instances = n_instances; d.first_id = first_id;
-    const PoolDesc pd = {(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &pd, sizeof pd, hipMemcpyHostToDevice));
+    ctx->pd = PoolDesc{(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};  // metadata and initial states cleared
+    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
     return RP_OK;
 }
 
@@ -5505,8 +5566,8 @@ extern "C" int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, cons
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     d.pool_wh = ctx->pool_wh; d.pool_area = ctx->pool_area; d.pool_max_h = ctx->pool_max_h;
     d.n_instances = n_instances; d.first_id = first_id;
-    const PoolDesc pd = {(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &pd, sizeof pd, hipMemcpyHostToDevice));
+    ctx->pd = PoolDesc{(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};  // metadata and initial states cleared
+    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
     return RP_OK;
 }
 
@@ -5523,10 +5584,52 @@ extern "C" int rp_set_instance_meta(rp_ctx *ctx, int64_t n, const uint64_t *epis
     if (n > 0 && bl) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_bl, bl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (n > 0 && has_buf) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_has, has_buf, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pd.episode_id = episode_id ? ctx->meta_id : nullptr; ctx->pd.bl = bl ? ctx->meta_bl : nullptr; ctx->pd.has_buf = has_buf ? ctx->meta_has : nullptr;
+    HIPCHK(ctx, hipMemcpy((void *)ctx->d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
+    return RP_OK;
+}
+
+extern "C" int rp_set_instance_initial(rp_ctx *ctx, int64_t n, const uint64_t *rows, const uint8_t *remaining, const int32_t *max_h) {
+    if (!ctx || !ctx->d.pool_wh || n != ctx->d.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: n must equal the size of the pool set last");
+    if ((rows == nullptr) != (remaining == nullptr)) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: rows and remaining go together (both NULL clears the initial states)");
     const DP &d = ctx->d;
-    const PoolDesc pd = {(long long)d.n_instances, (unsigned long long)d.first_id, d.pool_wh, d.pool_area, d.pool_max_h,
-                         episode_id ? ctx->meta_id : nullptr, bl ? ctx->meta_bl : nullptr, has_buf ? ctx->meta_has : nullptr};
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &pd, sizeof pd, hipMemcpyHostToDevice));
+    const size_t H = (size_t)d.H, N = (size_t)d.N;
+    std::vector<u64> rem((size_t)n * 2, 0ull);
+    std::vector<int> mh((size_t)n, 0);
+    if (rows) {
+        std::vector<u8> wh((size_t)n * N * 2);  // the pool's item sizes (a pool of generator seeds has them on the device only)
+        if (n > 0) HIPCHK(ctx, hipMemcpy(wh.data(), d.pool_wh, wh.size(), hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < n; ++k) {
+            for (size_t r = 0; r < H; ++r)
+                if (rows[(size_t)k * H + r] & ~full_mask(d.W))
+                    return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: row %d of instance %lld has a cell outside the %d columns", (int)r, (long long)k, d.W);
+            for (size_t i = 0; i < N; ++i) {
+                if (!remaining[(size_t)k * N + i]) continue;
+                rem[(size_t)k * 2 + i / 64] |= 1ull << (i % 64);
+                mh[k] = std::max(mh[k], (int)wh[((size_t)k * N + i) * 2 + 1]);  // getInitItems (BinPackingGame.py:48) over the items that take part
+            }
+            if (max_h) {
+                if (max_h[k] < 0) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: max_h[%lld] = %d is negative", (long long)k, max_h[k]);
+                mh[k] = max_h[k];
+            }
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // slots of the previous pool may still read the arrays
+    if (rows && n > ctx->init_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
+        ALLOC(ctx, ctx->init_rows, (size_t)n * H);
+        ALLOC(ctx, ctx->init_rem, (size_t)n * 2);
+        ALLOC(ctx, ctx->init_max_h, (size_t)n);
+        ctx->init_cap = n;
+    }
+    if (rows && n > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->init_rows, rows, (size_t)n * H * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->init_rem, rem.data(), (size_t)n * 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->init_max_h, mh.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const bool on = rows && n > 0;
+    ctx->pd.init_rows = on ? ctx->init_rows : nullptr; ctx->pd.init_rem = on ? ctx->init_rem : nullptr; ctx->pd.init_max_h = on ? ctx->init_max_h : nullptr;
+    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
     return RP_OK;
 }
 

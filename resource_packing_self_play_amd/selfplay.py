@@ -163,6 +163,7 @@ class BatchedSelfPlay:
         self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
         self._packings = []
         self._pool_items = None
+        self._pool_initial = None
         self.use_graph = bool(use_graph) and host_evaluator is None
         self.use_stem = bool(use_stem) and not rollout
         self.fuse_elementwise = bool(fuse_elementwise) and self.use_stem
@@ -279,6 +280,29 @@ class BatchedSelfPlay:
             has = np.asarray(thresholds[1])[lo:hi]
         g.eng.set_instance_meta(ids, bl, has)
 
+    def _set_initial(self, g, lo, hi, initial):
+        """Initial states (rows [n, H], remaining [n, N], max_h [n] or None) of group g's block lo:hi (rp_set_instance_initial)."""
+        if initial is None:
+            return
+        rows, rem, max_h = initial
+        g.eng.set_instance_initial(rows[lo:hi], rem[lo:hi], None if max_h is None else max_h[lo:hi])
+
+    def _check_initial(self, n, initial_rows, initial_remaining, max_h):
+        """-> (rows uint64 [n, H], remaining uint8 [n, N], max_h int32 [n] or None), or None without an initial state."""
+        if initial_rows is None and initial_remaining is None:
+            if max_h is not None:
+                raise ValueError("max_h belongs to an initial state: give initial_rows / initial_remaining")
+            return None
+        rows = np.zeros((n, self.H), np.uint64) if initial_rows is None else np.ascontiguousarray(initial_rows, dtype=np.uint64)
+        rem = np.ones((n, self.N), np.uint8) if initial_remaining is None else (np.asarray(initial_remaining) != 0).astype(np.uint8)
+        if rows.shape != (n, self.H) or rem.shape != (n, self.N):
+            raise ValueError("initial_rows must be [n, H] and initial_remaining [n, N]")
+        if max_h is not None:
+            max_h = np.ascontiguousarray(max_h, dtype=np.int32).reshape(-1)
+            if len(max_h) != n:
+                raise ValueError("max_h needs one entry per instance")
+        return rows, rem, max_h
+
     @staticmethod
     def _check_meta(n, episode_ids, thresholds):
         if episode_ids is not None and len(episode_ids) != n:
@@ -286,16 +310,22 @@ class BatchedSelfPlay:
         if thresholds is not None and (len(thresholds) != 2 or len(thresholds[0]) != n or len(thresholds[1]) != n):
             raise ValueError("thresholds must be (bl [n], has_buf [n])")
 
-    def start(self, item_wh, total_area, rewards_list=(), first_id=0, episode_ids=None, thresholds=None):
+    def start(self, item_wh, total_area, rewards_list=(), first_id=0, episode_ids=None, thresholds=None, initial_rows=None,
+              initial_remaining=None, max_h=None):
         """The pool is cut into one contiguous block per group; instance i's episode id is first_id + i, or episode_ids[i].
-        thresholds: (bl [n], has_buf [n]) -- instance i is ranked against that R2 threshold instead of rewards_list's."""
+        thresholds: (bl [n], has_buf [n]) -- instance i is ranked against that R2 threshold instead of rewards_list's.
+        initial_rows uint64 [n, H] / initial_remaining uint8 [n, N]: instance i starts from that state instead of the empty bin with
+        all items (rp_set_instance_initial; one of the two may be None: the empty bin / all items); total_area then includes the cells
+        already set.  max_h [n]: the episode's max_h where the default -- the largest h of the items that take part -- is not it."""
         item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8)
         total_area = np.ascontiguousarray(total_area, dtype=np.int32)
         buf = np.asarray(list(rewards_list), dtype=np.float64)
         self.first_id = int(first_id)
         self.n_instances = item_wh.shape[0]
         self._check_meta(self.n_instances, episode_ids, thresholds)
+        initial = self._check_initial(self.n_instances, initial_rows, initial_remaining, max_h)
         self._pool_items = (episode_ids, item_wh) if self.record_packings else None
+        self._pool_initial = initial
         torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -308,18 +338,23 @@ class BatchedSelfPlay:
             g.eng.set_rank_buffer(buf)
             g.eng.set_instance_pool(wh_g, area_g, self.first_id + lo)
             self._set_meta(g, lo, hi, episode_ids, thresholds)
+            self._set_initial(g, lo, hi, initial)
             g.eng._ck(g.eng.L.rp_begin_pool(g.eng.h))
 
-    def start_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, bin_w=None, episode_ids=None, thresholds=None):
+    def start_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, bin_w=None, episode_ids=None, thresholds=None, initial_rows=None,
+                         initial_remaining=None, max_h=None):
         """Like start(), with instance i = ItemsGenerator.items_generator(seeds[i]) of the bin_w x bin_h rectangle (default: the
         board) generated on the device (rp_set_instance_pool_seeds: bit-identical to the host generator, tests/test_gpu_rules.py);
-        total area bin_w * bin_h."""
+        total area bin_w * bin_h.  Seeded instances tile the bin, so they start from the empty bin: an initial state is refused."""
+        if initial_rows is not None or initial_remaining is not None or max_h is not None:
+            raise ValueError("a pool of generator seeds starts from the empty bin with all items: pass item_wh to start() for initial states")
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
         buf = np.asarray(list(rewards_list), dtype=np.float64)
         self.first_id = int(first_id)
         self.n_instances = seeds.shape[0]
         self._check_meta(self.n_instances, episode_ids, thresholds)
         self._pool_items = (episode_ids, (seeds, bin_w or self.W, bin_h or self.H)) if self.record_packings else None
+        self._pool_initial = None
         torch.cuda.synchronize(self.device)
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
             self.nnet.refresh_fused()
@@ -365,9 +400,11 @@ class BatchedSelfPlay:
             self._pool_items = (episode_ids, items)
         pool_ids = self.first_id + np.arange(self.n_instances, dtype=np.int64) if episode_ids is None else np.asarray(episode_ids, dtype=np.int64)
         index = {int(e): k for k, e in enumerate(pool_ids)}
+        initial = self._pool_initial
         for k in range(len(ids)):
-            m = int(moves[k])
-            self._packings.append(Packing(int(ids[k]), self.W, items[index[int(ids[k])]], action[k, :m], rows[k, :m], board[k], int(outcome[k]), float(score[k])))
+            m, i = int(moves[k]), index[int(ids[k])]
+            start = {} if initial is None else dict(initial_board=initial[0][i], present=initial[1][i] != 0)
+            self._packings.append(Packing(int(ids[k]), self.W, items[i], action[k, :m], rows[k, :m], board[k], int(outcome[k]), float(score[k]), **start))
 
     def pop_packings(self):
         """solve.Packing of every episode that finished (and was popped: run() does) since the last call, sorted by episode id."""
@@ -386,10 +423,11 @@ class BatchedSelfPlay:
                 tot[name] += val
         return tot
 
-    def run(self, item_wh, total_area, rewards_list=(), first_id=0, poll=16, max_steps=None, episode_ids=None, thresholds=None):
+    def run(self, item_wh, total_area, rewards_list=(), first_id=0, poll=16, max_steps=None, episode_ids=None, thresholds=None,
+            initial_rows=None, initial_remaining=None, max_h=None):
         """Plays every instance of the pool to the end.  Returns (episode ids, outcomes, scores, moves) sorted by id,
-        plus timing / counter statistics.  episode_ids / thresholds: see start()."""
-        self.start(item_wh, total_area, rewards_list, first_id, episode_ids, thresholds)
+        plus timing / counter statistics.  episode_ids / thresholds / initial_rows / initial_remaining / max_h: see start()."""
+        self.start(item_wh, total_area, rewards_list, first_id, episode_ids, thresholds, initial_rows, initial_remaining, max_h)
         return self._play_out(poll, max_steps)
 
     def run_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, poll=16, max_steps=None, bin_w=None, episode_ids=None,

@@ -25,9 +25,11 @@ class Packing:
     """One finished episode: which item went to which column, which bin rows it landed in, and the bin it left.
 
     Plain data: episode_id, W, item_wh uint8 [N, 2] (w, h), actions int32 [moves], rows uint64 [moves] (bit r = bin row r),
-    board uint64 [H] (bit c of board[r] = cell (r, c)), outcome (+-1, the ranked result), score."""
+    board uint64 [H] (bit c of board[r] = cell (r, c)), outcome (+-1, the ranked result), score; and where the episode started
+    (rp_set_instance_initial): initial_board uint64 [H], the cells set before the first move (default: none), and present bool [N],
+    the items that took part (default: all)."""
 
-    def __init__(self, episode_id, W, item_wh, actions, rows, board, outcome=0, score=0.0):
+    def __init__(self, episode_id, W, item_wh, actions, rows, board, outcome=0, score=0.0, initial_board=None, present=None):
         self.episode_id = int(episode_id)
         self.W = int(W)
         self.item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8).reshape(-1, 2)
@@ -35,10 +37,17 @@ class Packing:
         self.rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
         self.board = np.ascontiguousarray(board, dtype=np.uint64).reshape(-1)
         self.outcome, self.score = int(outcome), float(score)
+        self.initial_board = (np.zeros(len(self.board), np.uint64) if initial_board is None
+                              else np.ascontiguousarray(initial_board, dtype=np.uint64).reshape(-1))
+        self.present = (np.ones(len(self.item_wh), bool) if present is None else np.asarray(present).reshape(-1) != 0)
+        if self.initial_board.shape != self.board.shape or self.present.shape != (len(self.item_wh),):
+            raise ValueError("initial_board must have one row mask per bin row and present one flag per item")
         if self.actions.shape != self.rows.shape:
             raise ValueError("one rows mask per action")
         if len(self.actions) and (self.actions.min() < 0 or self.actions.max() >= self.W * len(self.item_wh)):
             raise ValueError("action outside the %d x %d action space" % (len(self.item_wh), self.W))
+        if len(self.actions) and not self.present[self.actions // self.W].all():
+            raise ValueError("a move places an item that does not take part")
 
     # ---- sizes ---------------------------------------------------------------------------------------
     @property
@@ -99,8 +108,8 @@ class Packing:
 
     # ---- boards --------------------------------------------------------------------------------------
     def board_after(self, m):
-        """Row masks uint64 [H] of the bin after moves 0..m (m = -1: the empty bin)."""
-        out = np.zeros(self.H, np.uint64)
+        """Row masks uint64 [H] of the bin after moves 0..m (m = -1: the initial board, the empty bin by default)."""
+        out = self.initial_board.copy()
         if m >= self.moves:
             raise IndexError("the episode has %d moves" % self.moves)
         bits = self._row_bits()
@@ -115,9 +124,12 @@ class Packing:
         return int(used[-1]) + 1 if len(used) else 1
 
     def layout(self):
-        """int8 [H, W]: index of the item that occupies each cell, -1 where the bin is empty.  Raises ValueError if two moves claim
-        one cell or if the cells of all moves are not exactly the final board."""
+        """int8 [H, W]: index of the item that occupies each cell, -1 where the bin is empty, -2 where the initial board had the cell
+        set.  Raises ValueError if two moves claim one cell, if a move claims an initially set cell, or if the cells of all moves and
+        the initial board are not exactly the final board."""
         out = np.full((self.H, self.W), -1, np.int8)
+        cols = np.arange(self.W, dtype=np.uint64)
+        out[((self.initial_board[:, None] >> cols[None, :]) & np.uint64(1)).astype(bool)] = -2
         bits = self._row_bits()
         for m in range(self.moves):
             self._span(m)
@@ -125,18 +137,19 @@ class Packing:
             for r in np.flatnonzero(bits[m]):
                 if (out[r, x:x + w] >= 0).any():
                     raise ValueError("move %d (item %d) overlaps item %d in row %d" % (m, it, int(out[r, x:x + w].max()), r))
+                if (out[r, x:x + w] == -2).any():
+                    raise ValueError("move %d (item %d) claims an initially set cell in row %d" % (m, it, r))
                 out[r, x:x + w] = it
-        cols = np.arange(self.W, dtype=np.uint64)
         final = ((self.board[:, None] >> cols[None, :]) & np.uint64(1)).astype(bool)
-        if not np.array_equal(out >= 0, final):
-            raise ValueError("the moves' cells differ from the final board in %d cells" % int(((out >= 0) != final).sum()))
+        if not np.array_equal(out != -1, final):
+            raise ValueError("the moves' and the initial board's cells differ from the final board in %d cells" % int(((out != -1) != final).sum()))
         return out
 
     def __str__(self):
         lay = self.layout()
-        sym = lambda i: "." if i < 0 else (_SYMBOLS[i] if i < len(_SYMBOLS) else "#")
+        sym = lambda i: "." if i == -1 else (_SYMBOLS[i] if 0 <= i < len(_SYMBOLS) else "#")  # '#': an initially set cell (or item 62+)
         head = "episode %d: %d of %d items placed, height %d of %d, score %.4f, outcome %+d" % (
-            self.episode_id, self.moves, self.N, self.height, self.H, self.score, self.outcome)
+            self.episode_id, self.moves, int(self.present.sum()), self.height, self.H, self.score, self.outcome)
         body = ["%3d |%s|" % (r, "".join(sym(int(c)) for c in lay[r])) for r in range(self.H - 1, -1, -1)]  # row 0 at the bottom
         return "\n".join([head] + body + ["    +" + "-" * self.W + "+"])
 
@@ -145,7 +158,7 @@ class Packing:
 
     def __eq__(self, other):
         return (isinstance(other, Packing) and self.episode_id == other.episode_id and self.W == other.W and self.outcome == other.outcome
-                and self.score == other.score and all(np.array_equal(getattr(self, k), getattr(other, k)) for k in ("item_wh", "actions", "rows", "board")))
+                and self.score == other.score and all(np.array_equal(getattr(self, k), getattr(other, k)) for k in ("item_wh", "actions", "rows", "board", "initial_board", "present")))
 
     __hash__ = None
 
@@ -158,26 +171,76 @@ def greedy_rule(args):
     return _lib.MOVE_ARGMAX_DRAW if tie == "draw" else _lib.MOVE_ARGMAX_FIRST
 
 
-def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin_w=None, rewards_list=(), first_id=0):
+def initial_state(W, H, N, item_wh, initial_board=None, remaining=None):
+    """The instances of pack() / random_scores() in the engine's form -> (item_wh uint8 [n, N, 2], rows uint64 [n, H] or None,
+    remaining uint8 [n, N] or None, total area int32 [n]).  item_wh: [n, N, 2], or ragged -- a list of [k_i, 2] arrays with k_i <= N,
+    padded with 1x1 items that do not take part.  initial_board: bool / uint8 [n, H, W] cells or uint64 [n, H] row masks; remaining:
+    uint8 [n, N].  rows and remaining are None when the instances start as always: the empty bin, all items.  The area is the set
+    cells of the initial board plus the area of the items that take part."""
+    n = len(item_wh)
+    wh = np.ones((n, N, 2), np.uint8)
+    rem = np.ones((n, N), np.uint8)
+    ragged = False
+    if isinstance(item_wh, np.ndarray) and item_wh.shape == (n, N, 2):  # the rectangular case in one copy
+        wh[:] = item_wh
+        item_wh = ()
+    for i, it in enumerate(item_wh):
+        it = np.asarray(it, dtype=np.uint8).reshape(-1, 2)
+        if len(it) > N:
+            raise ValueError("instance %d has %d items, the engine is built for %d" % (i, len(it), N))
+        wh[i, :len(it)] = it
+        rem[i, len(it):] = 0
+        ragged |= len(it) < N
+    if remaining is not None:
+        remaining = np.asarray(remaining)
+        if remaining.shape != (n, N):
+            raise ValueError("remaining must be [n, N]")
+        rem &= (remaining != 0).astype(np.uint8)
+    rows = None
+    if initial_board is not None:
+        b = np.asarray(initial_board)
+        if b.ndim == 3:  # cells
+            if b.shape != (n, H, W):
+                raise ValueError("initial_board cells must be [n, H, W]")
+            rows = ((b != 0).astype(np.uint64) << np.arange(W, dtype=np.uint64)[None, None, :]).sum(axis=2, dtype=np.uint64)
+        else:
+            rows = np.ascontiguousarray(b, dtype=np.uint64)
+            if rows.shape != (n, H):
+                raise ValueError("initial_board row masks must be [n, H]")
+    area = (wh[:, :, 0].astype(np.int32) * wh[:, :, 1] * rem).sum(axis=1).astype(np.int32)
+    if rows is not None:
+        cols = np.arange(W, dtype=np.uint64)
+        area = area + ((rows[:, :, None] >> cols[None, None, :]) & np.uint64(1)).sum(axis=(1, 2)).astype(np.int32)
+    if rows is None and remaining is None and not ragged:
+        return wh, None, None, area
+    return wh, (np.zeros((n, H), np.uint64) if rows is None else rows), rem, area
+
+
+def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin_w=None, rewards_list=(), first_id=0, initial_board=None,
+                  remaining=None):
     """Plays the instances through the driver `sp` (record_packings on) -> list[Packing] in instance order.  The driver's finished
-    ring holds four records per slot, so larger pools are played in runs of two per slot."""
+    ring holds four records per slot, so larger pools are played in runs of two per slot.  initial_board / remaining / ragged item_wh:
+    see pack()."""
     if (item_wh is None) == (seeds is None):
         raise ValueError("give either item_wh or seeds")
+    if seeds is not None and (initial_board is not None or remaining is not None):
+        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
     if not sp.record_packings:
         raise RuntimeError("the driver was built without record_packings")
     n = len(item_wh) if seeds is None else len(seeds)
+    rows0 = rem0 = None
+    if seeds is None:
+        item_wh, rows0, rem0, own_area = initial_state(sp.W, sp.H, sp.N, item_wh, initial_board, remaining)
     sp.pop_packings()
     out = []
     run = max(1, 2 * min(g.G for g in sp.groups) * len(sp.groups))
     for lo in range(0, n, run):
         hi = min(n, lo + run)
         if seeds is None:
-            wh = np.ascontiguousarray(item_wh, dtype=np.uint8)[lo:hi]
-            if total_area is None:
-                area = (wh[:, :, 0].astype(np.int32) * wh[:, :, 1]).sum(axis=1).astype(np.int32)
-            else:
-                area = np.asarray(total_area, np.int32).reshape(-1)[lo:hi]
-            sp.run(wh, area, rewards_list, first_id=first_id + lo)
+            wh = item_wh[lo:hi]
+            area = own_area[lo:hi] if total_area is None else np.asarray(total_area, np.int32).reshape(-1)[lo:hi]
+            sp.run(wh, area, rewards_list, first_id=first_id + lo, initial_rows=None if rows0 is None else rows0[lo:hi],
+                   initial_remaining=None if rem0 is None else rem0[lo:hi])
         else:
             sp.run_from_seeds(np.asarray(seeds, dtype=np.uint32)[lo:hi], rewards_list, first_id=first_id + lo, bin_h=bin_h, bin_w=bin_w)
         got = sp.pop_packings()
@@ -188,13 +251,17 @@ def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin
 
 
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
-         driver=None, seed=0, **driver_kw):
+         driver=None, seed=0, initial_board=None, remaining=None, **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
     item_wh: uint8 [n, N, 2] item sizes (w, h), total area = the items' own unless total_area [n] is given; or seeds [n]: instance i =
     ItemsGenerator.items_generator(seeds[i]) of the bin_w x bin_h rectangle (default: the board) cut on the device, total area
-    bin_w * bin_h (CoachBPP.py:119).  move_rule: default greedy per args.greedy_tie_break, as the reference's arena plays
+    bin_w * bin_h (CoachBPP.py:119).
+    Any start (item_wh only): item_wh may be ragged -- a list of [k_i, 2] arrays with k_i <= N; initial_board -- bool / uint8
+    [n, H, W] cells or uint64 [n, H] row masks -- are cells taken before the first move; remaining uint8 [n, N] marks the items that
+    take part.  The default total area is then the set cells plus the area of the items that take part.  An instance that has no
+    legal move from its start comes back as a Packing of 0 moves.  move_rule: default greedy per args.greedy_tie_break, as the reference's arena plays
     (greedy_a=0, CoachBPP.py:259); rewards_list: the R2 buffer the outcomes are ranked against.  A packing's score is not a function of
     it, but the search is: a terminal's value is its outcome against the buffer (and, on a tie, driver_kw's tie_salt), so another
     buffer can choose other moves.
@@ -205,6 +272,10 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     outcome of K random playouts per leaf (BatchedSelfPlay's evaluator="rollout").  The playouts are ranked against rewards_list too: with
     an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one."""
     from .selfplay import BatchedSelfPlay
+    if (item_wh is None) == (seeds is None):
+        raise ValueError("give either item_wh or seeds")
+    if seeds is not None and (initial_board is not None or remaining is not None):
+        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
@@ -215,33 +286,39 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     elif sp.move_rule != rule:
         sp.set_move_rule(rule)
     try:
-        return play_packings(sp, item_wh=item_wh, seeds=seeds, total_area=total_area, bin_h=bin_h, bin_w=bin_w, rewards_list=rewards_list)
+        return play_packings(sp, item_wh=item_wh, seeds=seeds, total_area=total_area, bin_h=bin_h, bin_w=bin_w, rewards_list=rewards_list,
+                             initial_board=initial_board, remaining=remaining)
     finally:
         if driver is None:
             sp.close()
 
 
-def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None):
-    """Scores of uniform random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin
+def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None, initial_board=None, remaining=None):
+    """Scores of uniform random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin, or
+    from (initial_board, remaining) as pack() takes them
     (rp_rollout_states; instance i plays as episode i, playout j draws from (seed, i, j)).  The random baseline a search or a trained
     network is compared with, and -- flattened -- a first R2 buffer for pack(..., evaluator="rollout", rewards_list=...).
     item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them."""
     if (item_wh is None) == (seeds is None):
         raise ValueError("give either item_wh or seeds")
+    if seeds is not None and (initial_board is not None or remaining is not None):
+        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
     W, H, N = game.bin_width, game.bin_height, game.num_items
+    rows0 = rem0 = None
+    if seeds is None:  # checked before an engine is built
+        item_wh, rows0, rem0, area = initial_state(W, H, N, item_wh, initial_board, remaining)
     eng = _lib.Engine(W, H, N, 1, 1, seed=int(seed) & 0x7FFFFFFFFFFFFFFF)
     try:
         if seeds is not None:
             item_wh = eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
             area = np.full(len(item_wh), int(bin_w or W) * int(bin_h or H), np.int32)
-        else:
-            item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8).reshape(-1, N, 2)
-            area = (item_wh[:, :, 0].astype(np.int32) * item_wh[:, :, 1]).sum(axis=1).astype(np.int32)
         n = len(item_wh)
         if n == 0:
             return np.zeros((0, int(playouts)), np.float64)
-        max_h = item_wh[:, :, 1].max(axis=1).astype(np.int32)
-        _, score, _, _ = eng.rollout_states(np.zeros((n, H), np.uint64), np.ones((n, N), np.uint8), item_wh, area, max_h, (), 0.75, playouts,
+        if rows0 is None:
+            rows0, rem0 = np.zeros((n, H), np.uint64), np.ones((n, N), np.uint8)
+        max_h = (item_wh[:, :, 1] * rem0).max(axis=1).astype(np.int32)  # over the items that take part, as rp_set_instance_initial
+        _, score, _, _ = eng.rollout_states(rows0, rem0, item_wh, area, max_h, (), 0.75, playouts,
                                             episode_id=np.arange(n, dtype=np.uint64), boards=False)
         return score
     finally:
