@@ -280,6 +280,10 @@ class Engine:
         mh = None if max_h is None else _arr(max_h, np.int32, (n,))
         self._ck(self.L.rp_set_instance_initial(self.h, n, _ptr(rows), _ptr(remaining), _ptr(mh)))
 
+    def begin_pool(self):
+        """Every slot takes its first instance of the pool set last (rp_begin_pool)."""
+        self._ck(self.L.rp_begin_pool(self.h))
+
     def set_roots(self, rows, remaining, first=0):
         rows = _arr(rows, np.uint64); count = rows.shape[0]
         rows = _arr(rows, np.uint64, (count, self.H)); remaining = _arr(remaining, np.uint8, (count, self.N))
@@ -488,6 +492,9 @@ class Engine:
         n, s = _i64(0), _i64(0)
         self._ck(self.L.rp_examples_packed_count(self.h, C.byref(n), C.byref(s)))
         return n.value, s.value
+
+    def examples_clear(self):
+        self._ck(self.L.rp_examples_clear(self.h))
 
     def examples_packed(self, device):
         """Everything recorded so far as a dict of device tensors in the packed layout of rp_examples_packed (+ episode, move)."""

@@ -71,7 +71,9 @@ struct NodeHdr {    // 32 bytes = two dwordx4 loads per visited node
 __host__ __device__ inline u32 hdr_term_kind(const NodeHdr &h) { return (h.flags >> 2) & 3u; }
 
 // Instance pool of auto_restart, in DEVICE memory: kernel arguments are baked into captured HIP graphs, the pool changes between
-// pools of one BatchedSelfPlay (size, episode-id base, even the buffers when it grows), so restarting slots read it from here.
+// pools of one BatchedSelfPlay (size, episode-id base, even the buffers when it grows), so restarting slots read it from here and the
+// DP carries nothing of the pool but this descriptor's address.  The host keeps one copy (rp_ctx::pool), written by the pool_*
+// functions only; pool_publish is the one place that copies it here.
 struct PoolDesc {
     long long n_instances;
     unsigned long long first_id;
@@ -155,11 +157,7 @@ struct DP {  // device view of a context, passed by value to every kernel
     // instance pool for auto_restart
     int auto_restart;
     int onehot_examples;  // greedy self-play records pi as a one-hot on the chosen action (MCTS_bpp.py:43-49)
-    long long n_instances;
-    u64 first_id;
-    const u8 *pool_wh;      // [n_instances][N][2]
-    const int *pool_area, *pool_max_h;
-    const PoolDesc *pool_desc;  // device copy of the five fields above (what the kernels read)
+    const PoolDesc *pool_desc;  // the pool in device memory; the host's copy and the buffers belong to rp_ctx::pool
     unsigned long long *next_instance;
     // replay buffer (CoachBPP.executeEpisode's trainExamples, CoachBPP.py:80,99)
     long long max_examples;
@@ -4193,26 +4191,30 @@ __global__ void __launch_bounds__(64 * WAVES) k_convpool32_wg(const float *__res
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// The instance pool of auto_restart on the host: the copy of *d.pool_desc that separate calls fill in (the pool, its metadata, its
+// initial states) and the device buffers it points into, each trio with its capacity in instances.  pd.wh != NULL = a pool is set.
+struct Pool {
+    PoolDesc pd = {};
+    int64_t cap = 0, meta_cap = 0, init_cap = 0;
+    u8 *wh = nullptr;  // rp_set_instance_pool[_seeds]
+    int *area = nullptr, *max_h = nullptr;
+    u64 *meta_id = nullptr;  // rp_set_instance_meta
+    double *meta_bl = nullptr;
+    u8 *meta_has = nullptr;
+    u64 *init_rows = nullptr, *init_rem = nullptr;  // rp_set_instance_initial
+    int *init_max_h = nullptr;
+};
+
 struct rp_ctx {
-    rp_config cfg;
-    DP d;
-    hipStream_t stream;
-    bool row64;
+    rp_config cfg = {};
+    DP d = {};
+    hipStream_t stream = nullptr;
+    bool row64 = false;
     std::string err;
     std::vector<void *> allocs;
-    int64_t bytes;
-    int64_t fin_popped;
-    u8 *pool_wh;
-    int *pool_area, *pool_max_h;
-    int64_t pool_cap;
-    u64 *meta_id;       // rp_set_instance_meta's arrays (capacity meta_cap)
-    double *meta_bl;
-    u8 *meta_has;
-    int64_t meta_cap;
-    u64 *init_rows = nullptr, *init_rem = nullptr;  // rp_set_instance_initial's arrays (capacity init_cap)
-    int *init_max_h = nullptr;
-    int64_t init_cap = 0;
-    PoolDesc pd = {};   // host copy of *d.pool_desc: the pool, its metadata and its initial states are set by separate calls
+    int64_t bytes = 0;
+    int64_t fin_popped = 0;
+    Pool pool;
     int n_cu = 256;                   // compute units and LDS bytes per CU of the device (hipDeviceProp, read once in rp_create)
     size_t lds_per_cu = 160 * 1024;
     int compact_rows = 0;             // rp_set_compact_rows: rp_search_step(ctx, NULL) lists the waiting slots on the device too
@@ -4616,12 +4618,23 @@ extern "C" const char *rp_last_error(const rp_ctx *ctx) { return ctx ? ctx->err.
 
 extern "C" int64_t rp_device_bytes(const rp_ctx *ctx) { return ctx ? ctx->bytes : 0; }
 
+static void free_ctx(rp_ctx *ctx) {
+    for (void *p : ctx->allocs) (void)hipFree(p);
+    delete ctx;
+}
+
+// rp_create's failure exits: the context's message (or the one fail(NULL, ...) left), then the context goes
+static int create_failed(rp_ctx *ctx, int code) {
+    const std::string msg = ctx->err.empty() ? g_create_error : ctx->err;
+    free_ctx(ctx);
+    return fail(nullptr, code, "%s", msg.c_str());
+}
+
 extern "C" void rp_destroy(rp_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : ctx->allocs) (void)hipFree(p);
-    delete ctx;
+    free_ctx(ctx);
 }
 
 extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
@@ -4638,13 +4651,9 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
         return fail(nullptr, RP_ERR_DEVICE, "no HIP device %d (found %d): the engine has no CPU fallback", cfg->device, ndev);
     rp_ctx *ctx = new rp_ctx();
     ctx->cfg = *cfg;
-    ctx->bytes = 0;
-    ctx->fin_popped = 0;
-    ctx->pool_wh = nullptr; ctx->pool_area = nullptr; ctx->pool_max_h = nullptr; ctx->pool_cap = 0;
-    ctx->meta_id = nullptr; ctx->meta_bl = nullptr; ctx->meta_has = nullptr; ctx->meta_cap = 0;
     ctx->stream = (hipStream_t)cfg->stream;
     hipError_t e = hipSetDevice(cfg->device);
-    if (e != hipSuccess) { delete ctx; return fail(nullptr, RP_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return create_failed(ctx, fail(ctx, RP_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(e)));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) {
@@ -4657,7 +4666,6 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
         }
     }
     DP &d = ctx->d;
-    memset(&d, 0, sizeof d);
     d.W = cfg->W; d.H = cfg->H; d.N = cfg->N; d.A = cfg->W * cfg->N; d.G = cfg->games; d.sims = cfg->sims;
     d.cpuct = cfg->cpuct; d.seed = cfg->seed; d.tie_salt = cfg->tie_salt; d.move_rule = cfg->move_rule;
     d.node_cap = cfg->node_cap > 0 ? cfg->node_cap : cfg->sims * (cfg->N + 1) + 2;
@@ -4673,11 +4681,10 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     d.n_pchunks = (d.edge_cap + d.pchunk - 1) / d.pchunk + (cfg->edge_cap > 0 ? 0 : cfg->N + 1);
     d.n_vchunks = (d.vis_cap + d.vchunk - 1) / d.vchunk + (cfg->vis_cap > 0 ? 0 : cfg->N + 1);
     d.n_pchunks = std::max(d.n_pchunks, 2); d.n_vchunks = std::max(d.n_vchunks, 2);
-    if (d.n_pchunks > 0xFFFE || d.n_vchunks > 0xFFFE) { delete ctx; return fail(nullptr, RP_ERR_ARG, "arena too large for 16-bit chunk ids"); }
+    if (d.n_pchunks > 0xFFFE || d.n_vchunks > 0xFFFE) return create_failed(ctx, fail(ctx, RP_ERR_ARG, "arena too large for 16-bit chunk ids"));
     d.edge_cap = d.n_pchunks * d.pchunk;
     d.vis_cap = d.n_vchunks * d.vchunk;
     d.reclaim = cfg->reclaim ? 1 : 0;
-    d.rows_identity = 0;
     int tc = 64;
     while (tc < 2 * d.node_cap) tc *= 2;
     d.table_cap = tc;
@@ -4689,7 +4696,7 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     d.magicW = (u32)(((1u << 20) + cfg->W - 1) / cfg->W);
     d.Hp = (cfg->H + 1) / 2; d.Wp = (cfg->W + 1) / 2;
     for (u32 a = 0; a < 8192u; ++a)
-        if (((a * d.magicW) >> 20) != a / (u32)cfg->W) { delete ctx; return fail(nullptr, RP_ERR_ARG, "internal: division magic"); }
+        if (((a * d.magicW) >> 20) != a / (u32)cfg->W) return create_failed(ctx, fail(ctx, RP_ERR_ARG, "internal: division magic"));
     const size_t G = (size_t)d.G, N = (size_t)d.N;
     int rc = RP_OK;
     auto A_ = [&](auto &ptr, size_t n) { if (rc == RP_OK) rc = dev_alloc(ctx, &ptr, n); };
@@ -4740,11 +4747,9 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     if ((int)llo.size() > MAX_LEAVES) rc = fail(nullptr, RP_ERR_ARG, "action space too large");
     size_t L = llo.size(), S = sd.size();
     if (rc != RP_OK) {
-        std::string msg = ctx->err.empty() ? g_create_error : ctx->err;
-        for (void *p : ctx->allocs) (void)hipFree(p);
-        delete ctx;
-        return fail(nullptr, rc, "rp_create: %s (needs about %.1f GiB of HBM)", msg.c_str(),
-                    (double)(G * ((size_t)d.node_cap * (32 + 4 * d.KW) + (size_t)d.edge_cap * 6 + (size_t)d.vis_cap * sizeof(VisEntry) + (size_t)d.table_cap * 8)) / (1 << 30));
+        const std::string msg = ctx->err.empty() ? g_create_error : ctx->err;
+        return create_failed(ctx, fail(ctx, rc, "rp_create: %s (needs about %.1f GiB of HBM)", msg.c_str(),
+                                       (double)(G * ((size_t)d.node_cap * (32 + 4 * d.KW) + (size_t)d.edge_cap * 6 + (size_t)d.vis_cap * sizeof(VisEntry) + (size_t)d.table_cap * 8)) / (1 << 30)));
     }
     // no chunk is open before the first episode begins
     (void)hipMemsetAsync(d.pa_cur, 0xFF, G * (N + 1) * sizeof(u16), ctx->stream); (void)hipMemsetAsync(d.pa_head, 0xFF, G * (N + 1) * sizeof(u16), ctx->stream);
@@ -4752,11 +4757,7 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     d.n_leaves = (int)L;
     for (size_t k = 0; k < L; ++k) { d.leaf_lo[k] = (u16)llo[k]; d.leaf_n[k] = (u8)ln[k]; }
     for (size_t k = 0; k < S; ++k) { d.sched_dst[k] = (u8)sd[k]; d.sched_src[k] = (u8)ss[k]; }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        for (void *p : ctx->allocs) (void)hipFree(p);
-        delete ctx;
-        return fail(nullptr, RP_ERR_DEVICE, "rp_create: device initialisation failed");
-    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return create_failed(ctx, fail(ctx, RP_ERR_DEVICE, "rp_create: device initialisation failed"));
     if (STAGE_BYTES(d) + 9 * 1024 > 64 * 1024) {  // A > ~6 900: static (8 KB) + staging LDS pass the default 64 KB limit
         const size_t lim = STAGE_BYTES(d) + 9 * 1024;
         const void *fns[5];
@@ -4764,24 +4765,14 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
         else { fns[0] = d.N > 64 ? (const void *)k_search<u32, true> : (const void *)k_search<u32, false>; fns[1] = (const void *)k_moves<u32>; fns[2] = (const void *)k_set_roots<u32>; fns[3] = (const void *)k_advance<u32>; fns[4] = (const void *)k_pool_begin<u32>; }
         for (const void *fn : fns) {
             const int rc2 = allow_lds(ctx, fn, lim, "rp_create (legal-move staging of the tree kernels)");
-            if (rc2 != RP_OK) {
-                const std::string msg = ctx->err;
-                for (void *p : ctx->allocs) (void)hipFree(p);
-                delete ctx;
-                return fail(nullptr, rc2, "%s", msg.c_str());
-            }
+            if (rc2 != RP_OK) return create_failed(ctx, rc2);
         }
     }
     if (d.A > 1536) {  // the LDS-row commit (rp_commit_eval_logits_wide) is these contexts' production route and first runs inside a graph capture
         CommitPlan pl{};
         int rc2 = plan_commit_lds(&pl, d.A, d.n_leaves, d.G, ctx->lds_per_cu) == COMMIT_PLAN_ARG ? fail(ctx, RP_ERR_ARG, "rp_create: no launch plan for the LDS-row commit") : RP_OK;
         if (rc2 == RP_OK) rc2 = allow_lds(ctx, commit_lds_kernel(ctx), pl.lds, "rp_create (LDS row of the commit kernel)");
-        if (rc2 != RP_OK) {
-            const std::string msg = ctx->err;
-            for (void *p : ctx->allocs) (void)hipFree(p);
-            delete ctx;
-            return fail(nullptr, rc2, "%s", msg.c_str());
-        }
+        if (rc2 != RP_OK) return create_failed(ctx, rc2);
     }
     *out = ctx;
     return RP_OK;
@@ -4818,6 +4809,25 @@ struct Scratch {
     }
 };
 #define NEED(ptr) do { if (!(ptr)) return fail(ctx, RP_ERR_DEVICE, "scratch allocation / upload failed"); } while (0)
+
+// Item sizes wh[n][N][2] of n instances.  With `who` (the entry point) every size must lie inside the grid: a larger one would shift by
+// more than the row's width.  mh, if given, receives per instance BinPackingGame.getInitItems' max_h (BinPackingGame.py:41-50): the
+// largest h over all items, or over those that take part (remaining[n][N] != 0).
+static int item_sizes(rp_ctx *ctx, const char *who, int64_t n, const u8 *wh, const u8 *remaining, int *mh) {
+    const DP &d = ctx->d;
+    for (int64_t k = 0; k < n; ++k) {
+        int top = 0;
+        for (int i = 0; i < d.N; ++i) {
+            const size_t at = (size_t)k * d.N + i;
+            const int w = wh[2 * at], h = wh[2 * at + 1];
+            if (who && (w < 1 || w > d.W || h < 1 || h > d.H))
+                return fail(ctx, RP_ERR_ARG, "%s: item %d of instance %lld has size %dx%d outside the %dx%d grid", who, i, (long long)k, w, h, d.W, d.H);
+            if (!remaining || remaining[at]) top = std::max(top, h);
+        }
+        if (mh) mh[k] = top;
+    }
+    return RP_OK;
+}
 
 extern "C" int rp_valid_moves(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
                               uint8_t *mask_out, int32_t *n_valid_out) {
@@ -4929,10 +4939,7 @@ extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, c
     const DP &d = ctx->d;
     const size_t n = (size_t)B * (size_t)playouts;
     if (n > (size_t)0x7FFFFFFF) return fail(ctx, RP_ERR_ARG, "rp_rollout_states: %lld states x %d playouts exceed 2^31 - 1", (long long)B, playouts);
-    for (size_t k = 0; k < (size_t)B * d.N; ++k) {  // sizes outside the grid would shift by more than the row's width
-        const int w = item_wh[2 * k], h = item_wh[2 * k + 1];
-        if (w < 1 || w > d.W || h < 1 || h > d.H) return fail(ctx, RP_ERR_ARG, "rp_rollout_states: item %lld has size %dx%d outside the %dx%d grid", (long long)k, w, h, d.W, d.H);
-    }
+    if (item_sizes(ctx, "rp_rollout_states", B, item_wh, nullptr, nullptr) != RP_OK) return RP_ERR_ARG;
     double bl = 0.0;
     bool has = rank_threshold(rewards, n_rewards, alpha, &bl);
     Scratch s(ctx);
@@ -4974,15 +4981,9 @@ extern "C" int rp_begin_episodes(rp_ctx *ctx, int32_t first, int32_t count, cons
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     std::vector<int> mh(count, 0);
+    if (item_sizes(ctx, "rp_begin_episodes", count, item_wh, nullptr, mh.data()) != RP_OK) return RP_ERR_ARG;
     std::vector<u64> ids(count);
-    for (int k = 0; k < count; ++k) {
-        for (int i = 0; i < d.N; ++i) {
-            int w = item_wh[((size_t)k * d.N + i) * 2], h = item_wh[((size_t)k * d.N + i) * 2 + 1];
-            if (w < 1 || w > d.W || h < 1 || h > d.H) return fail(ctx, RP_ERR_ARG, "item %d of episode %d has size %dx%d outside the %dx%d grid", i, k, w, h, d.W, d.H);
-            mh[k] = std::max(mh[k], h);  // BinPackingGame.getInitItems: max_h over ALL items (BinPackingGame.py:41-50)
-        }
-        ids[k] = episode_id ? episode_id[k] : (u64)(first + k);
-    }
+    for (int k = 0; k < count; ++k) ids[k] = episode_id ? episode_id[k] : (u64)(first + k);
     HIPCHK(ctx, hipMemcpyAsync(d.item_wh + (size_t)first * d.N * 2, item_wh, (size_t)count * d.N * 2, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d.total_area + first, total_area, (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d.max_h + first, mh.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -5483,43 +5484,62 @@ extern "C" int rp_pop_finished_packings(rp_ctx *ctx, int64_t max_n, uint64_t *ep
     return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out);
 }
 
+// The pool's three functions.  A setter makes every check that can refuse BEFORE pool_reserve: a refused call leaves the previous pool
+// in force.  pool_publish is the one place that copies the host descriptor to the device.
+static int pool_publish(rp_ctx *ctx) {
+    HIPCHK(ctx, hipMemcpy((void *)ctx->d.pool_desc, &ctx->pool.pd, sizeof(PoolDesc), hipMemcpyHostToDevice));
+    return RP_OK;
+}
+
+// room for n instances: slots of the previous pool may still read the arrays, outgrown buffers stay in ctx->allocs until destroy
+static int pool_reserve(rp_ctx *ctx, int64_t n) {
+    Pool &pl = ctx->pool;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n > pl.cap) {
+        ALLOC(ctx, pl.wh, (size_t)n * ctx->d.N * 2);
+        ALLOC(ctx, pl.area, (size_t)n);
+        ALLOC(ctx, pl.max_h, (size_t)n);
+        pl.cap = n;
+    }
+    return RP_OK;
+}
+
+// the filled buffers become the pool, drawn from its first instance, metadata and initial states cleared
+static int pool_install(rp_ctx *ctx, int64_t n, uint64_t first_id) {
+    Pool &pl = ctx->pool;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d.next_instance, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    pl.pd = PoolDesc{(long long)n, (unsigned long long)first_id, pl.wh, pl.area, pl.max_h};
+    return pool_publish(ctx);
+}
+
 extern "C" int rp_set_instance_pool(rp_ctx *ctx, int64_t n_instances, const uint8_t *item_wh, const int32_t *total_area, uint64_t first_id) {
     if (!ctx || n_instances < 0 || (n_instances > 0 && (!item_wh || !total_area))) return fail(ctx, RP_ERR_ARG, "rp_set_instance_pool: bad argument");
-    DP &d = ctx->d;
+    const Pool &pl = ctx->pool;
     std::vector<int> mh((size_t)n_instances, 0);
-    for (int64_t k = 0; k < n_instances; ++k)
-        for (int i = 0; i < d.N; ++i) {
-            int w = item_wh[((size_t)k * d.N + i) * 2], h = item_wh[((size_t)k * d.N + i) * 2 + 1];
-            if (w < 1 || w > d.W || h < 1 || h > d.H) return fail(ctx, RP_ERR_ARG, "item %d of instance %lld has size %dx%d outside the %dx%d grid", i, (long long)k, w, h, d.W, d.H);
-            mh[k] = std::max(mh[k], h);
-        }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_instances > ctx->pool_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
-        ALLOC(ctx, ctx->pool_wh, (size_t)n_instances * d.N * 2);
-        ALLOC(ctx, ctx->pool_area, (size_t)n_instances);
-        ALLOC(ctx, ctx->pool_max_h, (size_t)n_instances);
-        ctx->pool_cap = n_instances;
-    }
+    if (item_sizes(ctx, "rp_set_instance_pool", n_instances, item_wh, nullptr, mh.data()) != RP_OK) return RP_ERR_ARG;
+    int rc = pool_reserve(ctx, n_instances);
+    if (rc != RP_OK) return rc;
     if (n_instances > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pool_wh, item_wh, (size_t)n_instances * d.N * 2, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pool_area, total_area, (size_t)n_instances * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pool_max_h, mh.data(), (size_t)n_instances * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.wh, item_wh, (size_t)n_instances * ctx->d.N * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.area, total_area, (size_t)n_instances * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.max_h, mh.data(), (size_t)n_instances * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     }
-    HIPCHK(ctx, hipMemsetAsync(d.next_instance, 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    d.pool_wh = ctx->pool_wh; d.pool_area = ctx->pool_area; d.pool_max_h = ctx->pool_max_h;
-    d.n_instances = n_instances; d.first_id = first_id;
-    ctx->pd = PoolDesc{(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};  // metadata and initial states cleared
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
+    return pool_install(ctx, n_instances, first_id);
+}
+
+static int check_generator_rect(rp_ctx *ctx, int bin_w, int bin_h) {
+    const DP &d = ctx->d;
+    if (bin_w < 1 || bin_w > d.W || bin_h < 1 || bin_h > d.H || bin_w > 255 || bin_h > 255)
+        return fail(ctx, RP_ERR_ARG, "generator rectangle %dx%d does not fit the %dx%d grid", bin_w, bin_h, d.W, d.H);
+    if ((int64_t)bin_w * bin_h < d.N) return fail(ctx, RP_ERR_ARG, "a %dx%d rectangle cannot be cut into %d items", bin_w, bin_h, d.N);
     return RP_OK;
 }
 
 // instances from generator seeds into a DEVICE buffer [n][N][2] (shared by rp_generate_items and rp_set_instance_pool_seeds)
 static int generate_items_dev(rp_ctx *ctx, int64_t n, const uint32_t *seeds_host, int bin_w, int bin_h, u8 *out_dev) {
     const DP &d = ctx->d;
-    if (bin_w < 1 || bin_w > d.W || bin_h < 1 || bin_h > d.H || bin_w > 255 || bin_h > 255)
-        return fail(ctx, RP_ERR_ARG, "generator rectangle %dx%d does not fit the %dx%d grid", bin_w, bin_h, d.W, d.H);
-    if ((int64_t)bin_w * bin_h < d.N) return fail(ctx, RP_ERR_ARG, "a %dx%d rectangle cannot be cut into %d items", bin_w, bin_h, d.N);
+    if (check_generator_rect(ctx, bin_w, bin_h) != RP_OK) return RP_ERR_ARG;
     Scratch s(ctx);
     u32 *dseeds = s.up((const u32 *)seeds_host, (size_t)n); NEED(dseeds);
     u32 *dmt = s.up((const u32 *)nullptr, (size_t)n * 624); NEED(dmt);
@@ -5542,72 +5562,60 @@ extern "C" int rp_generate_items(rp_ctx *ctx, int64_t n, const uint32_t *seeds, 
 
 extern "C" int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, const uint32_t *seeds, int32_t bin_w, int32_t bin_h, uint64_t first_id) {
     if (!ctx || n_instances < 0 || (n_instances > 0 && !seeds)) return fail(ctx, RP_ERR_ARG, "rp_set_instance_pool_seeds: bad argument");
-    DP &d = ctx->d;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_instances > ctx->pool_cap) {
-        ALLOC(ctx, ctx->pool_wh, (size_t)n_instances * d.N * 2);
-        ALLOC(ctx, ctx->pool_area, (size_t)n_instances);
-        ALLOC(ctx, ctx->pool_max_h, (size_t)n_instances);
-        ctx->pool_cap = n_instances;
-    }
+    const Pool &pl = ctx->pool;
+    int rc = n_instances > 0 ? check_generator_rect(ctx, bin_w, bin_h) : RP_OK;  // refuses before a buffer is replaced
+    if (rc == RP_OK) rc = pool_reserve(ctx, n_instances);
+    if (rc != RP_OK) return rc;
     if (n_instances > 0) {
-        int rc = generate_items_dev(ctx, n_instances, seeds, bin_w, bin_h, ctx->pool_wh);
+        rc = generate_items_dev(ctx, n_instances, seeds, bin_w, bin_h, pl.wh);
         if (rc != RP_OK) return rc;
-        // total area = the generator rectangle (CoachBPP.py:119); max_h over all items (BinPackingGame.py:41-50)
-        std::vector<u8> wh((size_t)n_instances * d.N * 2);
-        HIPCHK(ctx, hipMemcpy(wh.data(), ctx->pool_wh, wh.size(), hipMemcpyDeviceToHost));
+        // total area = the generator rectangle (CoachBPP.py:119); max_h over all items
+        std::vector<u8> wh((size_t)n_instances * ctx->d.N * 2);
+        HIPCHK(ctx, hipMemcpy(wh.data(), pl.wh, wh.size(), hipMemcpyDeviceToHost));
         std::vector<int> area((size_t)n_instances, bin_w * bin_h), mh((size_t)n_instances, 0);
-        for (int64_t k = 0; k < n_instances; ++k)
-            for (int i = 0; i < d.N; ++i) mh[k] = std::max(mh[k], (int)wh[((size_t)k * d.N + i) * 2 + 1]);
-        HIPCHK(ctx, hipMemcpy(ctx->pool_area, area.data(), area.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(ctx->pool_max_h, mh.data(), mh.size() * sizeof(int), hipMemcpyHostToDevice));
+        item_sizes(ctx, nullptr, n_instances, wh.data(), nullptr, mh.data());
+        HIPCHK(ctx, hipMemcpy(pl.area, area.data(), area.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(pl.max_h, mh.data(), mh.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    HIPCHK(ctx, hipMemsetAsync(d.next_instance, 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    d.pool_wh = ctx->pool_wh; d.pool_area = ctx->pool_area; d.pool_max_h = ctx->pool_max_h;
-    d.n_instances = n_instances; d.first_id = first_id;
-    ctx->pd = PoolDesc{(long long)n_instances, (unsigned long long)first_id, ctx->pool_wh, ctx->pool_area, ctx->pool_max_h};  // metadata and initial states cleared
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
-    return RP_OK;
+    return pool_install(ctx, n_instances, first_id);
 }
 
 extern "C" int rp_set_instance_meta(rp_ctx *ctx, int64_t n, const uint64_t *episode_id, const double *bl, const uint8_t *has_buf) {
-    if (!ctx || !ctx->d.pool_wh || n != ctx->d.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_meta: n must equal the size of the pool set last");
+    if (!ctx || !ctx->pool.pd.wh || n != ctx->pool.pd.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_meta: n must equal the size of the pool set last");
+    Pool &pl = ctx->pool;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // slots of the previous pool may still read the arrays
-    if (n > ctx->meta_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
-        ALLOC(ctx, ctx->meta_id, (size_t)n);
-        ALLOC(ctx, ctx->meta_bl, (size_t)n);
-        ALLOC(ctx, ctx->meta_has, (size_t)n);
-        ctx->meta_cap = n;
+    if (n > pl.meta_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
+        ALLOC(ctx, pl.meta_id, (size_t)n);
+        ALLOC(ctx, pl.meta_bl, (size_t)n);
+        ALLOC(ctx, pl.meta_has, (size_t)n);
+        pl.meta_cap = n;
     }
-    if (n > 0 && episode_id) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_id, episode_id, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0 && bl) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_bl, bl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0 && has_buf) HIPCHK(ctx, hipMemcpyAsync(ctx->meta_has, has_buf, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0 && episode_id) HIPCHK(ctx, hipMemcpyAsync(pl.meta_id, episode_id, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0 && bl) HIPCHK(ctx, hipMemcpyAsync(pl.meta_bl, bl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0 && has_buf) HIPCHK(ctx, hipMemcpyAsync(pl.meta_has, has_buf, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pd.episode_id = episode_id ? ctx->meta_id : nullptr; ctx->pd.bl = bl ? ctx->meta_bl : nullptr; ctx->pd.has_buf = has_buf ? ctx->meta_has : nullptr;
-    HIPCHK(ctx, hipMemcpy((void *)ctx->d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
-    return RP_OK;
+    pl.pd.episode_id = episode_id ? pl.meta_id : nullptr; pl.pd.bl = bl ? pl.meta_bl : nullptr; pl.pd.has_buf = has_buf ? pl.meta_has : nullptr;
+    return pool_publish(ctx);
 }
 
 extern "C" int rp_set_instance_initial(rp_ctx *ctx, int64_t n, const uint64_t *rows, const uint8_t *remaining, const int32_t *max_h) {
-    if (!ctx || !ctx->d.pool_wh || n != ctx->d.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: n must equal the size of the pool set last");
+    if (!ctx || !ctx->pool.pd.wh || n != ctx->pool.pd.n_instances) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: n must equal the size of the pool set last");
     if ((rows == nullptr) != (remaining == nullptr)) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: rows and remaining go together (both NULL clears the initial states)");
     const DP &d = ctx->d;
+    Pool &pl = ctx->pool;
     const size_t H = (size_t)d.H, N = (size_t)d.N;
     std::vector<u64> rem((size_t)n * 2, 0ull);
     std::vector<int> mh((size_t)n, 0);
     if (rows) {
         std::vector<u8> wh((size_t)n * N * 2);  // the pool's item sizes (a pool of generator seeds has them on the device only)
-        if (n > 0) HIPCHK(ctx, hipMemcpy(wh.data(), d.pool_wh, wh.size(), hipMemcpyDeviceToHost));
+        if (n > 0) HIPCHK(ctx, hipMemcpy(wh.data(), pl.pd.wh, wh.size(), hipMemcpyDeviceToHost));
+        item_sizes(ctx, nullptr, n, wh.data(), remaining, mh.data());  // max_h over the items that take part
         for (int64_t k = 0; k < n; ++k) {
             for (size_t r = 0; r < H; ++r)
                 if (rows[(size_t)k * H + r] & ~full_mask(d.W))
                     return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: row %d of instance %lld has a cell outside the %d columns", (int)r, (long long)k, d.W);
-            for (size_t i = 0; i < N; ++i) {
-                if (!remaining[(size_t)k * N + i]) continue;
-                rem[(size_t)k * 2 + i / 64] |= 1ull << (i % 64);
-                mh[k] = std::max(mh[k], (int)wh[((size_t)k * N + i) * 2 + 1]);  // getInitItems (BinPackingGame.py:48) over the items that take part
-            }
+            for (size_t i = 0; i < N; ++i)
+                if (remaining[(size_t)k * N + i]) rem[(size_t)k * 2 + i / 64] |= 1ull << (i % 64);
             if (max_h) {
                 if (max_h[k] < 0) return fail(ctx, RP_ERR_ARG, "rp_set_instance_initial: max_h[%lld] = %d is negative", (long long)k, max_h[k]);
                 mh[k] = max_h[k];
@@ -5615,28 +5623,27 @@ extern "C" int rp_set_instance_initial(rp_ctx *ctx, int64_t n, const uint64_t *r
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // slots of the previous pool may still read the arrays
-    if (rows && n > ctx->init_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
-        ALLOC(ctx, ctx->init_rows, (size_t)n * H);
-        ALLOC(ctx, ctx->init_rem, (size_t)n * 2);
-        ALLOC(ctx, ctx->init_max_h, (size_t)n);
-        ctx->init_cap = n;
+    if (rows && n > pl.init_cap) {  // grow (old buffers stay in ctx->allocs until destroy)
+        ALLOC(ctx, pl.init_rows, (size_t)n * H);
+        ALLOC(ctx, pl.init_rem, (size_t)n * 2);
+        ALLOC(ctx, pl.init_max_h, (size_t)n);
+        pl.init_cap = n;
     }
     if (rows && n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->init_rows, rows, (size_t)n * H * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->init_rem, rem.data(), (size_t)n * 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->init_max_h, mh.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.init_rows, rows, (size_t)n * H * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.init_rem, rem.data(), (size_t)n * 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pl.init_max_h, mh.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     const bool on = rows && n > 0;
-    ctx->pd.init_rows = on ? ctx->init_rows : nullptr; ctx->pd.init_rem = on ? ctx->init_rem : nullptr; ctx->pd.init_max_h = on ? ctx->init_max_h : nullptr;
-    HIPCHK(ctx, hipMemcpy((void *)d.pool_desc, &ctx->pd, sizeof ctx->pd, hipMemcpyHostToDevice));
-    return RP_OK;
+    pl.pd.init_rows = on ? pl.init_rows : nullptr; pl.pd.init_rem = on ? pl.init_rem : nullptr; pl.pd.init_max_h = on ? pl.init_max_h : nullptr;
+    return pool_publish(ctx);
 }
 
 extern "C" int rp_begin_pool(rp_ctx *ctx) {
     if (!ctx) return RP_ERR_ARG;
     const DP &d = ctx->d;
-    if (!d.pool_wh) return fail(ctx, RP_ERR_STATE, "rp_begin_pool: no instance pool set");
+    if (!ctx->pool.pd.wh) return fail(ctx, RP_ERR_STATE, "rp_begin_pool: no instance pool set");
     DISPATCH_STAGED(ctx, k_pool_begin, grid_for(d.G), d);
     return check_device_error(ctx);
 }

@@ -310,6 +310,30 @@ class BatchedSelfPlay:
         if thresholds is not None and (len(thresholds) != 2 or len(thresholds[0]) != n or len(thresholds[1]) != n):
             raise ValueError("thresholds must be (bl [n], has_buf [n])")
 
+    def _start(self, n, set_block, items, rewards_list, first_id, episode_ids, thresholds, initial_rows=None, initial_remaining=None, max_h=None):
+        """start() and start_from_seeds(): set_block(g, lo, hi) sets group g's block lo:hi of the n instances as its engine's pool;
+        items is what pop_packings needs to give the item sizes back."""
+        buf = np.asarray(list(rewards_list), dtype=np.float64)
+        self.first_id = int(first_id)
+        self.n_instances = n
+        self._check_meta(n, episode_ids, thresholds)
+        initial = self._check_initial(n, initial_rows, initial_remaining, max_h)
+        self._pool_items = (episode_ids, items) if self.record_packings else None
+        self._pool_initial = initial
+        torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
+        if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
+            self.nnet.refresh_fused()
+            torch.cuda.synchronize(self.device)
+        for g, (lo, hi) in zip(self.groups, self._blocks(n)):
+            if self.host_evaluator is None and self.evaluator == "cnn":
+                with torch.cuda.stream(g.stream):
+                    g.refresh_weights(self.nnet)  # stem tables follow in-place weight updates
+            g.eng.set_rank_buffer(buf)
+            set_block(g, lo, hi)
+            self._set_meta(g, lo, hi, episode_ids, thresholds)
+            self._set_initial(g, lo, hi, initial)
+            g.eng.begin_pool()
+
     def start(self, item_wh, total_area, rewards_list=(), first_id=0, episode_ids=None, thresholds=None, initial_rows=None,
               initial_remaining=None, max_h=None):
         """The pool is cut into one contiguous block per group; instance i's episode id is first_id + i, or episode_ids[i].
@@ -319,27 +343,9 @@ class BatchedSelfPlay:
         already set.  max_h [n]: the episode's max_h where the default -- the largest h of the items that take part -- is not it."""
         item_wh = np.ascontiguousarray(item_wh, dtype=np.uint8)
         total_area = np.ascontiguousarray(total_area, dtype=np.int32)
-        buf = np.asarray(list(rewards_list), dtype=np.float64)
-        self.first_id = int(first_id)
-        self.n_instances = item_wh.shape[0]
-        self._check_meta(self.n_instances, episode_ids, thresholds)
-        initial = self._check_initial(self.n_instances, initial_rows, initial_remaining, max_h)
-        self._pool_items = (episode_ids, item_wh) if self.record_packings else None
-        self._pool_initial = initial
-        torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
-        if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
-            self.nnet.refresh_fused()
-            torch.cuda.synchronize(self.device)
-        for g, (lo, hi) in zip(self.groups, self._blocks(self.n_instances)):
-            wh_g = np.ascontiguousarray(item_wh[lo:hi]); area_g = np.ascontiguousarray(total_area[lo:hi])
-            if self.host_evaluator is None and self.evaluator == "cnn":
-                with torch.cuda.stream(g.stream):
-                    g.refresh_weights(self.nnet)  # stem tables follow in-place weight updates
-            g.eng.set_rank_buffer(buf)
-            g.eng.set_instance_pool(wh_g, area_g, self.first_id + lo)
-            self._set_meta(g, lo, hi, episode_ids, thresholds)
-            self._set_initial(g, lo, hi, initial)
-            g.eng._ck(g.eng.L.rp_begin_pool(g.eng.h))
+        self._start(item_wh.shape[0],
+                    lambda g, lo, hi: g.eng.set_instance_pool(np.ascontiguousarray(item_wh[lo:hi]), np.ascontiguousarray(total_area[lo:hi]), self.first_id + lo),
+                    item_wh, rewards_list, first_id, episode_ids, thresholds, initial_rows, initial_remaining, max_h)
 
     def start_from_seeds(self, seeds, rewards_list=(), first_id=0, bin_h=None, bin_w=None, episode_ids=None, thresholds=None, initial_rows=None,
                          initial_remaining=None, max_h=None):
@@ -349,24 +355,10 @@ class BatchedSelfPlay:
         if initial_rows is not None or initial_remaining is not None or max_h is not None:
             raise ValueError("a pool of generator seeds starts from the empty bin with all items: pass item_wh to start() for initial states")
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-        buf = np.asarray(list(rewards_list), dtype=np.float64)
-        self.first_id = int(first_id)
-        self.n_instances = seeds.shape[0]
-        self._check_meta(self.n_instances, episode_ids, thresholds)
-        self._pool_items = (episode_ids, (seeds, bin_w or self.W, bin_h or self.H)) if self.record_packings else None
-        self._pool_initial = None
-        torch.cuda.synchronize(self.device)
-        if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
-            self.nnet.refresh_fused()
-            torch.cuda.synchronize(self.device)
-        for g, (lo, hi) in zip(self.groups, self._blocks(self.n_instances)):
-            if self.host_evaluator is None and self.evaluator == "cnn":
-                with torch.cuda.stream(g.stream):
-                    g.refresh_weights(self.nnet)
-            g.eng.set_rank_buffer(buf)
-            g.eng.set_instance_pool_seeds(np.ascontiguousarray(seeds[lo:hi]), bin_w or self.W, bin_h or self.H, self.first_id + lo)
-            self._set_meta(g, lo, hi, episode_ids, thresholds)
-            g.eng._ck(g.eng.L.rp_begin_pool(g.eng.h))
+        bin_w, bin_h = bin_w or self.W, bin_h or self.H
+        self._start(seeds.shape[0],
+                    lambda g, lo, hi: g.eng.set_instance_pool_seeds(np.ascontiguousarray(seeds[lo:hi]), bin_w, bin_h, self.first_id + lo),
+                    (seeds, bin_w, bin_h), rewards_list, first_id, episode_ids, thresholds)
 
     def active(self):
         n = 0
@@ -472,4 +464,4 @@ class BatchedSelfPlay:
 
     def clear_examples(self):
         for g in self.groups:
-            g.eng._ck(g.eng.L.rp_examples_clear(g.eng.h))
+            g.eng.examples_clear()

@@ -216,15 +216,19 @@ def initial_state(W, H, N, item_wh, initial_board=None, remaining=None):
     return wh, (np.zeros((n, H), np.uint64) if rows is None else rows), rem, area
 
 
+def _check_instances(item_wh, seeds, initial_board, remaining):
+    if (item_wh is None) == (seeds is None):
+        raise ValueError("give either item_wh or seeds")
+    if seeds is not None and (initial_board is not None or remaining is not None):
+        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
+
+
 def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin_w=None, rewards_list=(), first_id=0, initial_board=None,
                   remaining=None):
     """Plays the instances through the driver `sp` (record_packings on) -> list[Packing] in instance order.  The driver's finished
     ring holds four records per slot, so larger pools are played in runs of two per slot.  initial_board / remaining / ragged item_wh:
     see pack()."""
-    if (item_wh is None) == (seeds is None):
-        raise ValueError("give either item_wh or seeds")
-    if seeds is not None and (initial_board is not None or remaining is not None):
-        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
+    _check_instances(item_wh, seeds, initial_board, remaining)
     if not sp.record_packings:
         raise RuntimeError("the driver was built without record_packings")
     n = len(item_wh) if seeds is None else len(seeds)
@@ -272,10 +276,7 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     outcome of K random playouts per leaf (BatchedSelfPlay's evaluator="rollout").  The playouts are ranked against rewards_list too: with
     an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one."""
     from .selfplay import BatchedSelfPlay
-    if (item_wh is None) == (seeds is None):
-        raise ValueError("give either item_wh or seeds")
-    if seeds is not None and (initial_board is not None or remaining is not None):
-        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
+    _check_instances(item_wh, seeds, initial_board, remaining)
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
@@ -299,10 +300,7 @@ def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=Non
     (rp_rollout_states; instance i plays as episode i, playout j draws from (seed, i, j)).  The random baseline a search or a trained
     network is compared with, and -- flattened -- a first R2 buffer for pack(..., evaluator="rollout", rewards_list=...).
     item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them."""
-    if (item_wh is None) == (seeds is None):
-        raise ValueError("give either item_wh or seeds")
-    if seeds is not None and (initial_board is not None or remaining is not None):
-        raise ValueError("instances from seeds tile the bin and start empty: an initial state needs item_wh")
+    _check_instances(item_wh, seeds, initial_board, remaining)
     W, H, N = game.bin_width, game.bin_height, game.num_items
     rows0 = rem0 = None
     if seeds is None:  # checked before an engine is built

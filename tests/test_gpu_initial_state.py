@@ -362,3 +362,119 @@ def test_refusals():
     with pytest.raises(ValueError):
         sp.start(np.full((2, N, 2), 2, np.uint8), [32, 32], max_h=[2, 2])
     sp.close()
+
+
+# ---- 7. one owner for the pool: the seeds setter's tail, growth, refusals ------------------------------------------------------------------
+NAME, SIMS = "10x10/8", 24
+
+
+def oracle_episodes(wh, ids):
+    """The oracle's sampled episodes of whole instances from the empty bin, as as_always() above -> [(actions, outcome, score)]."""
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    out = []
+    for k, e in enumerate(ids):
+        m = table_oracle(NAME)
+        m.begin_episode(wh[k, :, 0], wh[k, :, 1], W * H, BUF)
+        actions, _, o, s = m.play_episode(SIMS, policy=1, seed=SEED, episode_id=int(e), want_counts=False)
+        out.append(([int(a) for a in actions], o, s))
+        m.close()
+    return out
+
+
+def pool_engine():
+    from resource_packing_self_play_amd import _lib
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    eng = _lib.Engine(W, H, N, 4, SIMS, cpuct=1.0, alpha=rr.ALPHA, move_rule=_lib.MOVE_SAMPLE, seed=SEED, tie_salt=SALT, auto_restart=1)
+    eng.set_trace(True)
+    eng.set_rank_buffer(BUF)
+    return eng
+
+
+def play_pool(eng):
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    eng.begin_pool()
+    run_until_idle(eng, host_evaluator(lambda s: "hashed", W * N, lambda s: SALT))
+    eng.check()
+    return pop_records(eng)
+
+
+def assert_episodes(got, ids, want, where):
+    assert sorted(got) == sorted(int(e) for e in ids), where
+    for k, e in enumerate(ids):
+        o, s, mv, act, _, _ = got[int(e)]
+        assert ([int(a) for a in act[:mv]], o, s) == want[k], "%s instance %d" % (where, k)
+
+
+def test_seeds_pool_after_a_smaller_item_pool_with_metadata_and_initial_states():
+    from resource_packing_self_play_amd.binpacking.BinPackingGame import ItemsGenerator
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    first = make_pool(NAME, 3, "ebd", per_kind=1)  # instance 0 has no move from its start: a stale initial state would end it at once
+    wh1, area1, rows1, rem1 = pool_arrays(first)
+    seeds = np.arange(100, 109, dtype=np.uint32)  # 9 > 3: the pool's arrays grow
+    gen = ItemsGenerator(W, H, N)
+    wh2 = np.array([[it[:2] for it in gen.items_generator(int(sd))] for sd in seeds], dtype=np.uint8)
+    wh3 = np.stack([rr.make_items(NAME, np.random.default_rng(77))[0] for _ in range(2)])
+    ids2, ids3 = FIRST_ID + np.arange(9), 700 + np.arange(2)
+    want2, want3 = oracle_episodes(wh2, ids2), oracle_episodes(wh3, ids3)
+    assert all(len(w[0]) > 0 for w in want2 + want3) and want2[0][1] == -1  # a stale has_buf = 0 below would make that one +1
+    eng = pool_engine()
+    eng.set_instance_pool(wh1, area1, 0)
+    eng.set_instance_meta([900, 901, 902], [0.0, 0.0, 0.0], [0, 0, 0])
+    eng.set_instance_initial(rows1, rem1)
+    got1 = play_pool(eng)
+    assert sorted(got1) == [900, 901, 902] and got1[900][2] == 0  # metadata and initial states were in force
+    eng.set_instance_pool_seeds(seeds, first_id=FIRST_ID)
+    assert_episodes(play_pool(eng), ids2, want2, "seeds pool")
+    eng.set_instance_pool(wh3, np.full(2, W * H, np.int32), 700)
+    assert_episodes(play_pool(eng), ids3, want3, "last pool")
+    eng.close()
+
+
+def test_a_refused_pool_leaves_the_previous_one_in_force():
+    from resource_packing_self_play_amd import _lib
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    rng = np.random.default_rng(13)
+    wh = np.stack([rr.make_items(NAME, rng)[0] for _ in range(4)])
+    area = np.full(4, W * H, np.int32)
+    ids = np.array([31, 7, 1000, 12], np.uint64)
+    want = oracle_episodes(wh, ids)
+    eng = pool_engine()
+    eng.set_instance_pool(wh, area, FIRST_ID)
+    more = np.stack([rr.make_items(NAME, rng)[0] for _ in range(5)])
+    zero_w, tall = more.copy(), more.copy()
+    zero_w[3, 5, 0] = 0
+    tall[4, 0, 1] = H + 1
+    with pytest.raises(_lib.EngineError) as err:
+        eng.set_instance_pool_seeds(np.arange(9, dtype=np.uint32), bin_w=W + 1)  # 9 > 4: it would grow
+    assert err.value.code == _lib.ERR_ARG
+    for bad in (zero_w, tall):
+        with pytest.raises(_lib.EngineError) as err:
+            eng.set_instance_pool(bad, np.full(5, W * H, np.int32), 0)
+        assert err.value.code == _lib.ERR_ARG
+    eng.set_instance_meta(episode_id=ids)
+    assert_episodes(play_pool(eng), ids, want, "after three refusals")
+    eng.close()
+
+
+def test_item_size_refusals_name_the_item():
+    from resource_packing_self_play_amd import _lib
+    W, H, N, _ = rr.GEOMETRIES[NAME]
+    rng = np.random.default_rng(5)
+    wh = np.stack([rr.make_items(NAME, rng)[0] for _ in range(3)])
+    area = np.full(3, W * H, np.int32)
+    bad = wh.copy()
+    bad[1, 2, 0] = 0
+    rows, rem, max_h = np.zeros((3, H), np.uint64), np.ones((3, N), np.uint8), wh[:, :, 1].max(axis=1).astype(np.int32)
+    eng = pool_engine()
+    calls = [lambda x: eng.begin_episodes(x, area),
+             lambda x: eng.set_instance_pool(x, area),
+             lambda x: eng.rollout_states(rows, rem, x, area, max_h, BUF, rr.ALPHA, 1)]
+    for call in calls:
+        with pytest.raises(_lib.EngineError) as err:
+            call(bad)
+        assert err.value.code == _lib.ERR_ARG
+        msg = str(err.value)
+        assert "item 2" in msg and "0x%d" % bad[1, 2, 1] in msg and "%dx%d grid" % (W, H) in msg, msg
+        call(wh)  # and the valid call is served
+    eng.check()
+    eng.close()
