@@ -4478,25 +4478,25 @@ static StageKnobs stage_knobs(int entry) {
 
 // For the host-side tests of the plans, the dispatch rule and the LDS swizzle (not in include/rp_engine.h; no device needed).
 // out: family, nt, waves, cin, tail, imgw, wave_floats, lds, grid, block (all 0 unless the plan is PLAN_OK).
+static int plan_out(int rc, const StagePlan &plan, int64_t *out) {
+    const StagePlan p = rc == PLAN_OK ? plan : StagePlan{};
+    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
+    std::copy(f, f + 10, out);
+    return rc;
+}
 extern "C" int rp_debug_stage_plan(int32_t entry, int32_t Cin, int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail,
                                    int32_t pm_force, int64_t *out) {
     StagePlan p{};
     const StageDevice dev{n_cu, (size_t)lds_per_cu};
     const StageKnobs kn{wgs, tail, pm_force, 0, 0};  // the recorded plans (tests/golden/stage_plans.json) are k_convpool32's and k_resstage16's: rp_debug_convpool_plan and rp_debug_stage16_plan have the knobs
     const int rc = entry == 0 ? plan_resstage16(&p, B, H, W, dev, kn) : entry == 1 ? plan_convpool32(&p, B, Cin, H, W, dev, kn) : plan_resstage32(&p, B, H, W, dev, kn);
-    if (rc != PLAN_OK) p = StagePlan{};
-    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
-    std::copy(f, f + 10, out);
-    return rc;
+    return plan_out(rc, p, out);
 }
 extern "C" int rp_debug_convpool_plan(int32_t Cin, int64_t B, int32_t H, int32_t W, int32_t n_cu, int64_t lds_per_cu, int32_t wgs, int32_t tail, int32_t cp_pm,
                                       int64_t *out) {  // rp_debug_stage_plan's entry 1 with the RP_CONVPOOL_PM knob
     StagePlan p{};
     const int rc = plan_convpool32(&p, B, Cin, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, cp_pm, 0});
-    if (rc != PLAN_OK) p = StagePlan{};
-    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
-    std::copy(f, f + 10, out);
-    return rc;
+    return plan_out(rc, p, out);
 }
 extern "C" int rp_debug_stage32_pm_pick(int64_t B, int32_t H, int32_t W) {
     StagePlan p;
@@ -4507,10 +4507,7 @@ extern "C" int rp_debug_stage16_plan(int64_t B, int32_t H, int32_t W, int32_t n_
                                      int64_t *out) {  // rp_debug_stage_plan's entry 0 with the RP_STAGE16_PP knob
     StagePlan p{};
     const int rc = plan_resstage16(&p, B, H, W, StageDevice{n_cu, (size_t)lds_per_cu}, StageKnobs{wgs, tail, -1, 0, pp});
-    if (rc != PLAN_OK) p = StagePlan{};
-    const int64_t f[10] = {p.family, p.nt, p.waves, p.cin, p.tail, p.imgw, p.wave_floats, (int64_t)p.lds, p.grid, p.block};
-    std::copy(f, f + 10, out);
-    return rc;
+    return plan_out(rc, p, out);
 }
 // k_resstage16_pp's tables and addresses, from the functions the kernel uses.  Byte offsets count from the front guard of the image.
 extern "C" int rp_debug_stage16_pp_off(int32_t pos, int32_t leaf, int32_t quad) { return 4 * pp_off(pos, leaf, quad); }  // where (position, leaf, channel quad) is stored
@@ -4570,9 +4567,55 @@ extern "C" int rp_debug_commit_plan(int32_t A, int32_t n_leaves, int64_t G, int6
     std::copy(f, f + 8, out);
     return rc;
 }
-static const void *commit_lds_kernel(const rp_ctx *ctx) { return ctx->row64 ? (const void *)k_commit<u64, COMMIT_LOGITS_LDS> : (const void *)k_commit<u32, COMMIT_LOGITS_LDS>; }
 
 static int grid_for(long long waves) { return (int)((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
+
+// Every kernel launch of the host code: on the context's stream, the arguments converted to the kernel's parameter types, a launch
+// error reported with the kernel's name.
+template <class... P, class... A>
+static int launch(rp_ctx *ctx, const char *name, void (*fn)(P...), dim3 grid, dim3 block, size_t lds, const A &...args) {
+    hipLaunchKernelGGL(fn, grid, block, lds, ctx->stream, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RP_OK : fail(ctx, RP_ERR_DEVICE, "launch of %s failed: %s", name, hipGetErrorString(e));
+}
+// the usual shape: one wave per work item, WAVES_PER_BLOCK of them in a workgroup, no dynamic LDS
+template <class... P, class... A> static int launch_waves(rp_ctx *ctx, const char *name, void (*fn)(P...), long long waves, const A &...args) {
+    return launch(ctx, name, fn, dim3(grid_for(waves)), dim3(64 * WAVES_PER_BLOCK), 0, args...);
+}
+
+// A kernel's instantiation for the context's geometry: 64-bit rows beyond W = 32 and one flag (k_search and the rollout kernels: the
+// second item word beyond N = 64; k_leaf_stem: the item table in LDS; unused by kernels templated on the row type alone).  `pick`
+// names the instantiation from the tag it receives; a kernel's signature does not depend on its geometry, so the four answers have
+// one function pointer type.  GEO_KERNEL(ctx, flag, k_search<row_t, geo.flag>) writes the pick.
+template <class R, bool F> struct Geo { typedef R row_t; static constexpr bool flag = F; };
+template <class Pick> static auto by_geometry(const rp_ctx *ctx, bool flag, Pick pick) {
+    if (ctx->row64) return flag ? pick(Geo<u64, true>{}) : pick(Geo<u64, false>{});
+    return flag ? pick(Geo<u32, true>{}) : pick(Geo<u32, false>{});
+}
+#define GEO_KERNEL(ctx, flag, ...) by_geometry(ctx, flag, [](auto geo) { typedef typename decltype(geo)::row_t row_t; return __VA_ARGS__; })
+
+typedef void (*CommitFn)(DP, const float *, const float *);
+static CommitFn commit_kernel(const rp_ctx *ctx, int mode) {
+    if (mode == COMMIT_LOGITS_LDS) return GEO_KERNEL(ctx, false, k_commit<row_t, COMMIT_LOGITS_LDS>);
+    if (mode == COMMIT_LOGITS_REG) return GEO_KERNEL(ctx, false, k_commit<row_t, COMMIT_LOGITS_REG>);
+    return GEO_KERNEL(ctx, false, k_commit<row_t, COMMIT_PROBS>);
+}
+
+// The kernels that can create nodes stage a node's legal moves in LDS: WAVES_PER_BLOCK runs of A actions (STAGE_BYTES).  These are the
+// context's, named here and nowhere else: rp_create allows their LDS from this list (a launch may sit inside a graph capture, where the
+// attribute cannot be set), and launch_staged launches nothing that is not in it.
+struct StagedKernels { const void *fn[5]; };
+static StagedKernels staged_kernels(const rp_ctx *ctx) {
+    return {{(const void *)GEO_KERNEL(ctx, ctx->d.N > 64, k_search<row_t, geo.flag>), (const void *)GEO_KERNEL(ctx, false, k_moves<row_t>),
+             (const void *)GEO_KERNEL(ctx, false, k_set_roots<row_t>), (const void *)GEO_KERNEL(ctx, false, k_advance<row_t>),
+             (const void *)GEO_KERNEL(ctx, false, k_pool_begin<row_t>)}};
+}
+template <class... P, class... A> static int launch_staged(rp_ctx *ctx, const char *name, void (*fn)(P...), long long waves, const A &...args) {
+    const StagedKernels staged = staged_kernels(ctx);
+    if (std::find(staged.fn, staged.fn + 5, (const void *)fn) == staged.fn + 5)
+        return fail(ctx, RP_ERR_STATE, "%s stages legal moves in LDS but is not in staged_kernels(): rp_create has not allowed its LDS", name);
+    return launch(ctx, name, fn, dim3(grid_for(waves)), dim3(64 * WAVES_PER_BLOCK), STAGE_BYTES(ctx->d), args...);
+}
 
 // Dynamic LDS above the default 64 KB limit has to be allowed per kernel; a size the device cannot give is an argument error with
 // the figures in the message, not a launch failure later.
@@ -4760,10 +4803,8 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return create_failed(ctx, fail(ctx, RP_ERR_DEVICE, "rp_create: device initialisation failed"));
     if (STAGE_BYTES(d) + 9 * 1024 > 64 * 1024) {  // A > ~6 900: static (8 KB) + staging LDS pass the default 64 KB limit
         const size_t lim = STAGE_BYTES(d) + 9 * 1024;
-        const void *fns[5];
-        if (ctx->row64) { fns[0] = d.N > 64 ? (const void *)k_search<u64, true> : (const void *)k_search<u64, false>; fns[1] = (const void *)k_moves<u64>; fns[2] = (const void *)k_set_roots<u64>; fns[3] = (const void *)k_advance<u64>; fns[4] = (const void *)k_pool_begin<u64>; }
-        else { fns[0] = d.N > 64 ? (const void *)k_search<u32, true> : (const void *)k_search<u32, false>; fns[1] = (const void *)k_moves<u32>; fns[2] = (const void *)k_set_roots<u32>; fns[3] = (const void *)k_advance<u32>; fns[4] = (const void *)k_pool_begin<u32>; }
-        for (const void *fn : fns) {
+        const StagedKernels staged = staged_kernels(ctx);
+        for (const void *fn : staged.fn) {
             const int rc2 = allow_lds(ctx, fn, lim, "rp_create (legal-move staging of the tree kernels)");
             if (rc2 != RP_OK) return create_failed(ctx, rc2);
         }
@@ -4771,44 +4812,43 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     if (d.A > 1536) {  // the LDS-row commit (rp_commit_eval_logits_wide) is these contexts' production route and first runs inside a graph capture
         CommitPlan pl{};
         int rc2 = plan_commit_lds(&pl, d.A, d.n_leaves, d.G, ctx->lds_per_cu) == COMMIT_PLAN_ARG ? fail(ctx, RP_ERR_ARG, "rp_create: no launch plan for the LDS-row commit") : RP_OK;
-        if (rc2 == RP_OK) rc2 = allow_lds(ctx, commit_lds_kernel(ctx), pl.lds, "rp_create (LDS row of the commit kernel)");
+        if (rc2 == RP_OK) rc2 = allow_lds(ctx, (const void *)commit_kernel(ctx, COMMIT_LOGITS_LDS), pl.lds, "rp_create (LDS row of the commit kernel)");
         if (rc2 != RP_OK) return create_failed(ctx, rc2);
     }
     *out = ctx;
     return RP_OK;
 }
 
-#define DISPATCH(ctx, kernel, grid, ...)                                                                   \
-    do {                                                                                                   \
-        if ((ctx)->row64) hipLaunchKernelGGL(kernel<u64>, dim3(grid), dim3(64 * WAVES_PER_BLOCK), 0, (ctx)->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel<u32>, dim3(grid), dim3(64 * WAVES_PER_BLOCK), 0, (ctx)->stream, __VA_ARGS__);              \
-        hipError_t le_ = hipGetLastError();                                                                \
-        if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of %s failed: %s", #kernel, hipGetErrorString(le_)); \
-    } while (0)
-
-#define DISPATCH_STAGED(ctx, kernel, grid, ...)                                                            \
-    do {                                                                                                   \
-        if ((ctx)->row64) hipLaunchKernelGGL(kernel<u64>, dim3(grid), dim3(64 * WAVES_PER_BLOCK), STAGE_BYTES((ctx)->d), (ctx)->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel<u32>, dim3(grid), dim3(64 * WAVES_PER_BLOCK), STAGE_BYTES((ctx)->d), (ctx)->stream, __VA_ARGS__);              \
-        hipError_t le_ = hipGetLastError();                                                                \
-        if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of %s failed: %s", #kernel, hipGetErrorString(le_)); \
-    } while (0)
-
-// scratch device copies of host inputs for the stateless calls
+// Scratch device arrays of the stateless calls: in() uploads a host array, out() allocates one and remembers where finish() copies it
+// back to (nowhere with host == NULL).  A failed allocation or upload is remembered: one ok() before the launch reports it.  finish()
+// enqueues the copies back and synchronises, after which the host arrays are valid and the scratch may go.
 struct Scratch {
+    struct Back { void *host; const void *dev; size_t bytes; };
     rp_ctx *ctx;
+    bool failed = false;
     std::vector<void *> ptrs;
+    std::vector<Back> backs;
     explicit Scratch(rp_ctx *c) : ctx(c) {}
     ~Scratch() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> T *up(const T *host, size_t n) {
+    template <typename T> T *in(const T *host, size_t n) {
+        T *p = out((T *)nullptr, n);
+        if (p && hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) failed = true;
+        return p;
+    }
+    template <typename T> T *out(T *host, size_t n) {
         void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { failed = true; return nullptr; }
         ptrs.push_back(p);
-        if (host && hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+        if (host) backs.push_back(Back{host, p, n * sizeof(T)});
         return (T *)p;
     }
+    int ok() const { return failed ? fail(ctx, RP_ERR_DEVICE, "scratch allocation / upload failed") : RP_OK; }
+    int finish() {
+        for (const Back &b : backs) HIPCHK(ctx, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return RP_OK;
+    }
 };
-#define NEED(ptr) do { if (!(ptr)) return fail(ctx, RP_ERR_DEVICE, "scratch allocation / upload failed"); } while (0)
 
 // Item sizes wh[n][N][2] of n instances.  With `who` (the entry point) every size must lie inside the grid: a larger one would shift by
 // more than the row's width.  mh, if given, receives per instance BinPackingGame.getInitItems' max_h (BinPackingGame.py:41-50): the
@@ -4835,16 +4875,14 @@ extern "C" int rp_valid_moves(rp_ctx *ctx, int64_t B, const uint64_t *rows, cons
     if (B == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)rows, (size_t)B * d.H); NEED(drows);
-    u8 *drem = s.up(remaining, (size_t)B * d.N); NEED(drem);
-    u8 *dwh = s.up(item_wh, (size_t)B * d.N * 2); NEED(dwh);
-    u8 *dmask = s.up((const u8 *)nullptr, (size_t)B * d.A); NEED(dmask);
-    int *dnv = s.up((const int *)nullptr, (size_t)B); NEED(dnv);
-    DISPATCH(ctx, k_valid_moves, grid_for(B), d, (long long)B, drows, drem, dwh, dmask, dnv);
-    HIPCHK(ctx, hipMemcpyAsync(mask_out, dmask, (size_t)B * d.A, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_valid_out) HIPCHK(ctx, hipMemcpyAsync(n_valid_out, dnv, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    u8 *dmask = s.out(mask_out, (size_t)B * d.A);
+    int *dnv = s.out(n_valid_out, (size_t)B);  // optional for the caller, written by the kernel either way
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_valid_moves", GEO_KERNEL(ctx, false, k_valid_moves<row_t>), B, d, B, drows, drem, dwh, dmask, dnv);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_apply_move(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
@@ -4854,19 +4892,16 @@ extern "C" int rp_apply_move(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
     if (B == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)rows, (size_t)B * d.H); NEED(drows);
-    u8 *drem = s.up(remaining, (size_t)B * d.N); NEED(drem);
-    u8 *dwh = s.up(item_wh, (size_t)B * d.N * 2); NEED(dwh);
-    int *dact = s.up(action, (size_t)B); NEED(dact);
-    u64 *drows_o = s.up((const u64 *)nullptr, (size_t)B * d.H); NEED(drows_o);
-    u8 *drem_o = s.up((const u8 *)nullptr, (size_t)B * d.N); NEED(drem_o);
-    int *dst = s.up((const int *)nullptr, (size_t)B); NEED(dst);
-    DISPATCH(ctx, k_apply_move, grid_for(B), d, (long long)B, drows, drem, dwh, dact, drows_o, drem_o, dst);
-    HIPCHK(ctx, hipMemcpyAsync(rows_out, drows_o, (size_t)B * d.H * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(remaining_out, drem_o, (size_t)B * d.N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(status_out, dst, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    int *dact = s.in(action, (size_t)B);
+    u64 *drows_o = s.out((u64 *)rows_out, (size_t)B * d.H);
+    u8 *drem_o = s.out(remaining_out, (size_t)B * d.N);
+    int *dst = s.out(status_out, (size_t)B);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_apply_move", GEO_KERNEL(ctx, false, k_apply_move<row_t>), B, d, B, drows, drem, dwh, dact, drows_o, drem_o, dst);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 // sorted[int(floor(len*alpha)) - 1] with Python's negative-index wrap (BinPackingGame.py:205-206)
@@ -4892,30 +4927,19 @@ extern "C" int rp_game_ended(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
     double bl = 0.0;
     bool has = rank_threshold(rewards, n_rewards, alpha, &bl);
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)rows, (size_t)B * d.H); NEED(drows);
-    u8 *drem = s.up(remaining, (size_t)B * d.N); NEED(drem);
-    u8 *dwh = s.up(item_wh, (size_t)B * d.N * 2); NEED(dwh);
-    int *darea = s.up(total_area, (size_t)B); NEED(darea);
-    int *dmh = s.up(max_h, (size_t)B); NEED(dmh);
-    int *dend = s.up((const int *)nullptr, (size_t)B); NEED(dend);
-    double *drew = s.up((const double *)nullptr, (size_t)B); NEED(drew);
-    DISPATCH(ctx, k_game_ended, grid_for(B), d, (long long)B, drows, drem, dwh, darea, dmh, has ? 1 : 0, bl, dend, drew);
-    HIPCHK(ctx, hipMemcpyAsync(ended_out, dend, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(reward_out, drew, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    int *darea = s.in(total_area, (size_t)B);
+    int *dmh = s.in(max_h, (size_t)B);
+    int *dend = s.out(ended_out, (size_t)B);
+    double *drew = s.out(reward_out, (size_t)B);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_game_ended", GEO_KERNEL(ctx, false, k_game_ended<row_t>), B, d, B, drows, drem, dwh, darea, dmh, has ? 1 : 0, bl, dend, drew);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 #define RP_MAX_PLAYOUTS 256
-// k_rollout / k_rollout_states instance of the context's geometry (64-bit rows beyond W = 32, the second item word beyond N = 64)
-#define DISPATCH_ROLLOUT(ctx, kernel, grid, ...)                                                           \
-    do {                                                                                                   \
-        const dim3 grid_(grid), block_(64 * WAVES_PER_BLOCK);                                              \
-        if ((ctx)->row64) { if ((ctx)->d.N > 64) hipLaunchKernelGGL((kernel<u64, true>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); else hipLaunchKernelGGL((kernel<u64, false>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); } \
-        else { if ((ctx)->d.N > 64) hipLaunchKernelGGL((kernel<u32, true>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); else hipLaunchKernelGGL((kernel<u32, false>), grid_, block_, 0, (ctx)->stream, __VA_ARGS__); } \
-        hipError_t le_ = hipGetLastError();                                                                \
-        if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of %s failed: %s", #kernel, hipGetErrorString(le_)); \
-    } while (0)
 
 extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, float *v_dev, int64_t capacity_rows) {
     if (!ctx || !v_dev || capacity_rows < 0) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: bad argument");
@@ -4923,8 +4947,8 @@ extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, flo
     const DP &d = ctx->d;
     long long rows = std::min<long long>(capacity_rows, d.G);
     if (rows == 0) return RP_OK;
-    DISPATCH_ROLLOUT(ctx, k_rollout, (unsigned)rows, d, (int)playouts, pi_dev, v_dev, (long long)capacity_rows);
-    return RP_OK;
+    return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev, v_dev,
+                  capacity_rows);
 }
 
 extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
@@ -4943,35 +4967,28 @@ extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, c
     double bl = 0.0;
     bool has = rank_threshold(rewards, n_rewards, alpha, &bl);
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)rows, (size_t)B * d.H); NEED(drows);
-    u8 *drem = s.up(remaining, (size_t)B * d.N); NEED(drem);
-    u8 *dwh = s.up(item_wh, (size_t)B * d.N * 2); NEED(dwh);
-    int *darea = s.up(total_area, (size_t)B); NEED(darea);
-    int *dmh = s.up(max_h, (size_t)B); NEED(dmh);
-    u64 *dep = nullptr;
-    if (episode_id) { dep = s.up((const u64 *)episode_id, (size_t)B); NEED(dep); }
-    int *dout = s.up((const int *)nullptr, n); NEED(dout);
-    double *dscore = s.up((const double *)nullptr, n); NEED(dscore);
-    int *dmoves = s.up((const int *)nullptr, n); NEED(dmoves);
-    u64 *dboard = nullptr;
-    if (board_out) { dboard = s.up((const u64 *)nullptr, n * d.H); NEED(dboard); }
-    DISPATCH_ROLLOUT(ctx, k_rollout_states, (unsigned)grid_for((long long)n), d, (long long)B, (int)playouts, (const u64 *)drows, (const u8 *)drem,
-                     (const u8 *)dwh, (const int *)darea, (const int *)dmh, (const u64 *)dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
-    HIPCHK(ctx, hipMemcpyAsync(outcome_out, dout, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(score_out, dscore, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(moves_out, dmoves, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (board_out) HIPCHK(ctx, hipMemcpyAsync(board_out, dboard, n * d.H * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    int *darea = s.in(total_area, (size_t)B);
+    int *dmh = s.in(max_h, (size_t)B);
+    u64 *dep = episode_id ? s.in((const u64 *)episode_id, (size_t)B) : nullptr;
+    int *dout = s.out(outcome_out, n);
+    double *dscore = s.out(score_out, n);
+    int *dmoves = s.out(moves_out, n);
+    u64 *dboard = board_out ? s.out((u64 *)board_out, n * d.H) : nullptr;
+    int rc = s.ok();
+    if (rc == RP_OK)
+        rc = launch_waves(ctx, "k_rollout_states", GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag>), (long long)n, d, B, playouts, drows, drem, dwh, darea, dmh,
+                          dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_set_rank_buffer(rp_ctx *ctx, const double *rewards, int32_t n) {
     if (!ctx || n < 0 || (n > 0 && !rewards)) return fail(ctx, RP_ERR_ARG, "rp_set_rank_buffer: bad argument");
     double bl = 0.0;
     int has = rank_threshold(rewards, n, ctx->cfg.alpha, &bl) ? 1 : 0;
-    hipLaunchKernelGGL(k_fill_rank, dim3((ctx->d.G + 255) / 256), dim3(256), 0, ctx->stream, ctx->d, bl, has);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_fill_rank", k_fill_rank, dim3((ctx->d.G + 255) / 256), dim3(256), 0, ctx->d, bl, has);
 }
 
 extern "C" int rp_begin_episodes(rp_ctx *ctx, int32_t first, int32_t count, const uint8_t *item_wh, const int32_t *total_area,
@@ -4988,9 +5005,9 @@ extern "C" int rp_begin_episodes(rp_ctx *ctx, int32_t first, int32_t count, cons
     HIPCHK(ctx, hipMemcpyAsync(d.total_area + first, total_area, (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d.max_h + first, mh.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d.episode + first, ids.data(), (size_t)count * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    DISPATCH_STAGED(ctx, k_set_roots, grid_for(count), d, (int)first, (int)count, (const u64 *)nullptr, (const u8 *)nullptr, 1);
+    const int rc = launch_staged(ctx, "k_set_roots", GEO_KERNEL(ctx, false, k_set_roots<row_t>), count, d, first, count, nullptr, nullptr, 1);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
-    return check_device_error(ctx);
+    return rc == RP_OK ? check_device_error(ctx) : rc;
 }
 
 extern "C" int rp_set_roots(rp_ctx *ctx, int32_t first, int32_t count, const uint64_t *rows, const uint8_t *remaining) {
@@ -4998,11 +5015,12 @@ extern "C" int rp_set_roots(rp_ctx *ctx, int32_t first, int32_t count, const uin
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)rows, (size_t)count * d.H); NEED(drows);
-    u8 *drem = s.up(remaining, (size_t)count * d.N); NEED(drem);
-    DISPATCH_STAGED(ctx, k_set_roots, grid_for(count), d, (int)first, (int)count, (const u64 *)drows, (const u8 *)drem, 0);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return check_device_error(ctx);
+    u64 *drows = s.in((const u64 *)rows, (size_t)count * d.H);
+    u8 *drem = s.in(remaining, (size_t)count * d.N);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_staged(ctx, "k_set_roots", GEO_KERNEL(ctx, false, k_set_roots<row_t>), count, d, first, count, drows, drem, 0);
+    if (rc == RP_OK) rc = s.finish();
+    return rc == RP_OK ? check_device_error(ctx) : rc;
 }
 
 extern "C" int rp_set_stream(rp_ctx *ctx, void *stream) {
@@ -5085,26 +5103,18 @@ extern "C" int rp_last_values(rp_ctx *ctx, int32_t first, int32_t count, double 
 extern "C" int rp_search_step(rp_ctx *ctx, int32_t *n_leaves_out) {
     if (!ctx) return RP_ERR_ARG;
     DP &d = ctx->d;
-    if (d.move_rule != RP_MOVE_EXTERNAL) DISPATCH_STAGED(ctx, k_moves, grid_for(d.G), d);
-    {
-        const dim3 grid(grid_for(d.G)), block(64 * WAVES_PER_BLOCK);
-        const size_t lds = STAGE_BYTES(d);
-        if (ctx->row64) { if (d.N > 64) hipLaunchKernelGGL((k_search<u64, true>), grid, block, lds, ctx->stream, d); else hipLaunchKernelGGL((k_search<u64, false>), grid, block, lds, ctx->stream, d); }
-        else { if (d.N > 64) hipLaunchKernelGGL((k_search<u32, true>), grid, block, lds, ctx->stream, d); else hipLaunchKernelGGL((k_search<u32, false>), grid, block, lds, ctx->stream, d); }
-        hipError_t le_ = hipGetLastError();
-        if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of k_search failed: %s", hipGetErrorString(le_));
-    }
+    int rc = d.move_rule != RP_MOVE_EXTERNAL ? launch_staged(ctx, "k_moves", GEO_KERNEL(ctx, false, k_moves<row_t>), d.G, d) : RP_OK;
+    if (rc == RP_OK) rc = launch_staged(ctx, "k_search", GEO_KERNEL(ctx, d.N > 64, k_search<row_t, geo.flag>), d.G, d);
+    if (rc != RP_OK) return rc;
     // Without a count request nothing is synchronised and evaluator row b belongs to slot b (fixed shapes for graph capture);
     // with one, the waiting slots are listed in slot order and rows follow that list.
     d.rows_identity = (n_leaves_out || ctx->compact_rows) ? 0 : 1;
-    if (!d.rows_identity) {
-        hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, d);
-        HIPCHK(ctx, hipGetLastError());
-    }
+    if (!d.rows_identity) rc = launch(ctx, "k_compact", k_compact, dim3(1), dim3(1024), 0, d);
+    if (rc != RP_OK) return rc;
     if (n_leaves_out) {
         int n = 0;
         HIPCHK(ctx, hipMemcpyAsync(&n, d.eval_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        int rc = check_device_error(ctx);  // synchronises
+        rc = check_device_error(ctx);  // synchronises
         if (rc != RP_OK) return rc;
         *n_leaves_out = n;
     }
@@ -5116,8 +5126,7 @@ extern "C" int rp_leaf_planes(rp_ctx *ctx, float *planes_dev, int64_t capacity_r
     const DP &d = ctx->d;
     long long rows = std::min<long long>(capacity_rows, d.G);
     if (rows == 0) return RP_OK;
-    DISPATCH(ctx, k_leaf_planes, grid_for(rows), d, planes_dev, (long long)capacity_rows);
-    return RP_OK;
+    return launch_waves(ctx, "k_leaf_planes", GEO_KERNEL(ctx, false, k_leaf_planes<row_t>), rows, d, planes_dev, capacity_rows);
 }
 
 extern "C" int rp_leaf_count_async(rp_ctx *ctx, int32_t *count_host) {
@@ -5136,9 +5145,7 @@ extern "C" int rp_stem_set_weights(rp_ctx *ctx, const float *conv_w_dev, const f
         ALLOC(ctx, d.stemScale, (size_t)STEM_C);
     }
     const size_t tbl_lds = ((size_t)d.N * 25 + 512) * sizeof(double);  // 29.7 KB at N = 128
-    hipLaunchKernelGGL(k_stem_tables, dim3(STEM_C), dim3(256), tbl_lds, ctx->stream, d.N, conv_w_dev, bias_dev, d.stemT, d.stemTB, d.stemBias, d.stemScale);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_stem_tables", k_stem_tables, dim3(STEM_C), dim3(256), tbl_lds, d.N, conv_w_dev, bias_dev, d.stemT, d.stemTB, d.stemBias, d.stemScale);
 }
 
 extern "C" int rp_leaf_stem(rp_ctx *ctx, float *out_dev, float *out_relu_dev, int64_t capacity_rows, int32_t channels_last) {
@@ -5151,15 +5158,8 @@ extern "C" int rp_leaf_stem(rp_ctx *ctx, float *out_dev, float *out_relu_dev, in
     const bool t_lds = t_bytes <= 64 * 1024;
     // LDS form: persistent workgroups, 3 per CU (3 x 51 KB of LDS at N = 32), a wave per leaf; L2 form: a workgroup per leaf
     const int grid = (int)std::min<long long>(t_lds ? grid_for(rows) : rows, t_lds ? ctx->n_cu * STEM_WAVES : 1 << 20);
-    if (ctx->row64) {
-        if (t_lds) hipLaunchKernelGGL((k_leaf_stem<u64, true>), dim3(grid), dim3(64 * WAVES_PER_BLOCK), t_bytes, ctx->stream, d, out_dev, out_relu_dev, (long long)capacity_rows, (int)(channels_last != 0));
-        else hipLaunchKernelGGL((k_leaf_stem<u64, false>), dim3(grid), dim3(64 * WAVES_PER_BLOCK), 0, ctx->stream, d, out_dev, out_relu_dev, (long long)capacity_rows, (int)(channels_last != 0));
-    } else {
-        if (t_lds) hipLaunchKernelGGL((k_leaf_stem<u32, true>), dim3(grid), dim3(64 * WAVES_PER_BLOCK), t_bytes, ctx->stream, d, out_dev, out_relu_dev, (long long)capacity_rows, (int)(channels_last != 0));
-        else hipLaunchKernelGGL((k_leaf_stem<u32, false>), dim3(grid), dim3(64 * WAVES_PER_BLOCK), 0, ctx->stream, d, out_dev, out_relu_dev, (long long)capacity_rows, (int)(channels_last != 0));
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_leaf_stem", GEO_KERNEL(ctx, t_lds, k_leaf_stem<row_t, geo.flag>), dim3(grid), dim3(64 * WAVES_PER_BLOCK), t_lds ? t_bytes : 0, d, out_dev, out_relu_dev,
+                  capacity_rows, channels_last != 0);
 }
 
 extern "C" int rp_nn_bias_relu(rp_ctx *ctx, float *x_dev, const float *bias_dev, int64_t B, int32_t C, int32_t HW) {
@@ -5167,9 +5167,7 @@ extern "C" int rp_nn_bias_relu(rp_ctx *ctx, float *x_dev, const float *bias_dev,
     long long n = (long long)B * C * HW;
     if (n % 4) return fail(ctx, RP_ERR_ARG, "rp_nn_bias_relu: element count must be a multiple of 4");
     if (n == 0) return RP_OK;
-    hipLaunchKernelGGL(k_nn_bias_relu, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ctx->stream, x_dev, bias_dev, n / 4, (int)C, (int)HW);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_nn_bias_relu", k_nn_bias_relu, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, x_dev, bias_dev, n / 4, C, HW);
 }
 
 extern "C" int rp_nn_bias_residual(rp_ctx *ctx, const float *x_dev, const float *bias_dev, const float *res_dev, float *out_dev, float *out_relu_dev,
@@ -5178,10 +5176,8 @@ extern "C" int rp_nn_bias_residual(rp_ctx *ctx, const float *x_dev, const float 
     long long n = (long long)B * C * HW;
     if (n % 4) return fail(ctx, RP_ERR_ARG, "rp_nn_bias_residual: element count must be a multiple of 4");
     if (n == 0) return RP_OK;
-    hipLaunchKernelGGL(k_nn_bias_residual, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ctx->stream, x_dev, bias_dev, res_dev, out_dev, out_relu_dev,
-                       n / 4, (int)C, (int)HW);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_nn_bias_residual", k_nn_bias_residual, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, x_dev, bias_dev, res_dev, out_dev, out_relu_dev, n / 4, C,
+                  HW);
 }
 
 extern "C" int rp_nn_bias_pool(rp_ctx *ctx, const float *x_dev, const float *bias_dev, float *out_dev, float *out_relu_dev, int64_t B, int32_t C, int32_t H,
@@ -5191,32 +5187,21 @@ extern "C" int rp_nn_bias_pool(rp_ctx *ctx, const float *x_dev, const float *bia
     long long n = (long long)B * C * Hp * Wp;
     if (n == 0) return RP_OK;
     if (channels_last && C % 4 == 0 && n / 4 < 0xFFFFFF00LL)
-        hipLaunchKernelGGL(k_nn_bias_pool_nhwc4, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ctx->stream, (const float4 *)x_dev, (const float4 *)bias_dev,
-                           (float4 *)out_dev, (float4 *)out_relu_dev, (unsigned)(n / 4), (unsigned)(C / 4), (int)H, (int)W, Hp, Wp);
-    else if (channels_last)
-        hipLaunchKernelGGL(k_nn_bias_pool_nhwc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x_dev, bias_dev, out_dev, out_relu_dev, n, (int)C,
-                           (int)H, (int)W, Hp, Wp);
-    else
-        hipLaunchKernelGGL(k_nn_bias_pool, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x_dev, bias_dev, out_dev, out_relu_dev, n, (int)C, (int)H,
-                           (int)W, Hp, Wp);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+        return launch(ctx, "k_nn_bias_pool_nhwc4", k_nn_bias_pool_nhwc4, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (const float4 *)x_dev, (const float4 *)bias_dev,
+                      (float4 *)out_dev, (float4 *)out_relu_dev, n / 4, C / 4, H, W, Hp, Wp);
+    return launch(ctx, channels_last ? "k_nn_bias_pool_nhwc" : "k_nn_bias_pool", channels_last ? k_nn_bias_pool_nhwc : k_nn_bias_pool, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                  x_dev, bias_dev, out_dev, out_relu_dev, n, C, H, W, Hp, Wp);
 }
 
 extern "C" int rp_nn_value_head(rp_ctx *ctx, const float *z_dev, const float *w_dev, const float *bias_dev, float *out_dev, int64_t B, int32_t K) {
     if (!ctx || !z_dev || !w_dev || !bias_dev || !out_dev || B < 0 || K < 4 || K % 4) return fail(ctx, RP_ERR_ARG, "rp_nn_value_head: bad argument (K a multiple of 4)");
     if (B == 0) return RP_OK;
-    hipLaunchKernelGGL(k_nn_value_head, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, ctx->stream, (const float4 *)z_dev, (const float4 *)w_dev, bias_dev, out_dev,
-                       (long long)B, (int)(K / 4));
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_nn_value_head", k_nn_value_head, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (const float4 *)z_dev, (const float4 *)w_dev, bias_dev, out_dev, B, K / 4);
 }
 
 extern "C" int rp_nn_pack_conv16(rp_ctx *ctx, const float *w_dev, float *frag_dev) {
     if (!ctx || !w_dev || !frag_dev) return fail(ctx, RP_ERR_ARG, "rp_nn_pack_conv16: bad argument");
-    hipLaunchKernelGGL(k_pack_conv16, dim3(9), dim3(256), 0, ctx->stream, w_dev, frag_dev);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_pack_conv16", k_pack_conv16, dim3(9), dim3(256), 0, w_dev, frag_dev);
 }
 
 extern "C" int rp_nn_resblock16(rp_ctx *ctx, const float *x_dev, const float *frag0_dev, const float *bias0_dev, const float *frag1_dev, const float *bias1_dev,
@@ -5228,10 +5213,7 @@ extern "C" int rp_nn_resblock16(rp_ctx *ctx, const float *x_dev, const float *fr
     { const int rc = allow_lds(ctx, (const void *)k_resblock16, lds, "rp_nn_resblock16"); if (rc != RP_OK) return rc; }
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ctx->lds_per_cu / lds));
     const int grid = (int)std::min<long long>((B + 3) / 4, (long long)ctx->n_cu * per_cu);
-    hipLaunchKernelGGL(k_resblock16, dim3(grid), dim3(256), lds, ctx->stream, x_dev, frag0_dev, bias0_dev, frag1_dev, bias1_dev, out_dev, out_relu_dev, (long long)B,
-                       (int)H, (int)W);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_resblock16", k_resblock16, dim3(grid), dim3(256), lds, x_dev, frag0_dev, bias0_dev, frag1_dev, bias1_dev, out_dev, out_relu_dev, B, H, W);
 }
 
 // A stage kernel family's instantiations by the plan fields that are its template arguments; the kernels of a table share a signature.
@@ -5260,15 +5242,13 @@ static const StageEntry<StagePmFn> RS32_PM_TABLE[] = {rs32_pm<3>(), rs32_pm<5>()
 static const StageEntry<StagePmFn> RS16_PP_TABLE[] = {{50, 4, 16, 0, k_resstage16_pp}};
 static const StageEntry<StageFn> RS32_TABLE[] = {rs32<1>(), rs32<2>(), rs32<3>(), rs32<4>(), rs32<5>()};
 
-// The plan's kernel from its family's table: LDS allowance, launch, launch error.  The arguments convert to the kernel's parameter types.
+// The plan's kernel from its family's table: LDS allowance, then the launch (a launch error names the entry point: the table has no names).
 template <class... P, size_t N, class... A>
 static int launch_stage(rp_ctx *ctx, const char *what, const StagePlan &p, const StageEntry<void (*)(P...)> (&table)[N], A... args) {
     for (const auto &e : table) {
         if (e.nt != p.nt || e.waves != p.waves || e.cin != p.cin || e.tail != p.tail) continue;
-        { const int rc = allow_lds(ctx, (const void *)e.fn, p.lds, what); if (rc != RP_OK) return rc; }
-        hipLaunchKernelGGL(e.fn, dim3(p.grid), dim3(p.block), p.lds, ctx->stream, args...);
-        HIPCHK(ctx, hipGetLastError());
-        return RP_OK;
+        const int rc = allow_lds(ctx, (const void *)e.fn, p.lds, what);
+        return rc == RP_OK ? launch(ctx, what, e.fn, dim3(p.grid), dim3(p.block), p.lds, args...) : rc;
     }
     return fail(ctx, RP_ERR_ARG, "%s: unsupported image size", what);
 }
@@ -5295,9 +5275,7 @@ extern "C" int rp_nn_resstage16(rp_ctx *ctx, const float *x_dev, const float *fr
 extern "C" int rp_nn_pack_conv32(rp_ctx *ctx, const float *w_dev, float *frag_dev, int32_t Cin) {
     if (!ctx || !w_dev || !frag_dev || (Cin != 16 && Cin != 32)) return fail(ctx, RP_ERR_ARG, "rp_nn_pack_conv32: bad argument (Cin 16 or 32)");
     const int n = 9 * Cin * 32;
-    hipLaunchKernelGGL(k_pack_conv32, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, w_dev, frag_dev, (int)Cin);
-    HIPCHK(ctx, hipGetLastError());
-    return RP_OK;
+    return launch(ctx, "k_pack_conv32", k_pack_conv32, dim3((n + 255) / 256), dim3(256), 0, w_dev, frag_dev, Cin);
 }
 
 extern "C" int rp_nn_convpool32(rp_ctx *ctx, const float *x_dev, const float *frag_dev, const float *bias_dev, float *out_dev, int64_t B, int32_t Cin, int32_t H,
@@ -5335,15 +5313,12 @@ extern "C" int rp_leaf_states(rp_ctx *ctx, int32_t max_rows, uint64_t *rows_out,
     *n_out = n;
     if (n == 0) return RP_OK;
     Scratch s(ctx);
-    u64 *drows = s.up((const u64 *)nullptr, (size_t)n * d.H); NEED(drows);
-    u8 *drem = s.up((const u8 *)nullptr, (size_t)n * d.N); NEED(drem);
-    int *dslot = s.up((const int *)nullptr, (size_t)n); NEED(dslot);
-    DISPATCH(ctx, k_leaf_states, grid_for(n), d, drows, drem, dslot, n);
-    HIPCHK(ctx, hipMemcpyAsync(rows_out, drows, (size_t)n * d.H * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(remaining_out, drem, (size_t)n * d.N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(slot_out, dslot, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u64 *drows = s.out((u64 *)rows_out, (size_t)n * d.H);
+    u8 *drem = s.out(remaining_out, (size_t)n * d.N);
+    int *dslot = s.out(slot_out, (size_t)n);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_leaf_states", GEO_KERNEL(ctx, false, k_leaf_states<row_t>), n, d, drows, drem, dslot, n);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 static int launch_commit(rp_ctx *ctx, const float *pi_dev, const float *v_dev, int mode) {
@@ -5355,22 +5330,11 @@ static int launch_commit(rp_ctx *ctx, const float *pi_dev, const float *v_dev, i
         // no hipFuncSetAttribute here: the launch may sit inside a graph capture, and rp_create has allowed what A > 1536 asks for
         if (rc == COMMIT_PLAN_LDS)
             return fail(ctx, RP_ERR_ARG, "rp_commit_eval_logits_wide: needs %zu bytes of LDS per workgroup, the device has %zu per CU", pl.lds, ctx->lds_per_cu);
-        if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_LOGITS_LDS>), dim3(pl.grid), dim3(pl.block), pl.lds, ctx->stream, d, pi_dev, v_dev);
-        else hipLaunchKernelGGL((k_commit<u32, COMMIT_LOGITS_LDS>), dim3(pl.grid), dim3(pl.block), pl.lds, ctx->stream, d, pi_dev, v_dev);
-    } else {
-        const dim3 grid(grid_for(d.G)), block(64 * WAVES_PER_BLOCK);  // one wave per slot; waiting slots find their evaluator row in game_row
-        const size_t lds = (size_t)WAVES_PER_BLOCK * commit_wave_lds(d.A, d.n_leaves, mode == COMMIT_LOGITS_REG ? (size_t)d.A : 0).total();
-        if (mode == COMMIT_LOGITS_REG) {
-            if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_LOGITS_REG>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-            else hipLaunchKernelGGL((k_commit<u32, COMMIT_LOGITS_REG>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-        } else {
-            if (ctx->row64) hipLaunchKernelGGL((k_commit<u64, COMMIT_PROBS>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-            else hipLaunchKernelGGL((k_commit<u32, COMMIT_PROBS>), grid, block, lds, ctx->stream, d, pi_dev, v_dev);
-        }
+        return launch(ctx, "k_commit", commit_kernel(ctx, mode), dim3(pl.grid), dim3(pl.block), pl.lds, d, pi_dev, v_dev);
     }
-    hipError_t le_ = hipGetLastError();
-    if (le_ != hipSuccess) return fail(ctx, RP_ERR_DEVICE, "launch of k_commit failed: %s", hipGetErrorString(le_));
-    return RP_OK;
+    // one wave per slot; waiting slots find their evaluator row in game_row
+    const size_t lds = (size_t)WAVES_PER_BLOCK * commit_wave_lds(d.A, d.n_leaves, mode == COMMIT_LOGITS_REG ? (size_t)d.A : 0).total();
+    return launch(ctx, "k_commit", commit_kernel(ctx, mode), dim3(grid_for(d.G)), dim3(64 * WAVES_PER_BLOCK), lds, d, pi_dev, v_dev);
 }
 
 extern "C" int rp_commit_eval(rp_ctx *ctx, const float *pi_dev, const float *v_dev) {
@@ -5400,11 +5364,12 @@ extern "C" int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const floa
     if (n_rows < n) return fail(ctx, RP_ERR_ARG, "rp_commit_eval_host: %d rows given, %d leaves waiting", n_rows, n);
     if (n == 0) return RP_OK;
     Scratch s(ctx);
-    float *dpi = s.up(pi_host, (size_t)n * d.A); NEED(dpi);
-    float *dv = s.up(v_host, (size_t)n); NEED(dv);
-    { const int rc = launch_commit(ctx, dpi, dv, COMMIT_PROBS); if (rc != RP_OK) return rc; }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return check_device_error(ctx);
+    float *dpi = s.in(pi_host, (size_t)n * d.A);
+    float *dv = s.in(v_host, (size_t)n);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_commit(ctx, dpi, dv, COMMIT_PROBS);
+    if (rc == RP_OK) rc = s.finish();
+    return rc == RP_OK ? check_device_error(ctx) : rc;
 }
 
 extern "C" int rp_root_counts(rp_ctx *ctx, int32_t first, int32_t count, uint32_t *counts_out) {
@@ -5412,12 +5377,10 @@ extern "C" int rp_root_counts(rp_ctx *ctx, int32_t first, int32_t count, uint32_
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    u32 *dc = s.up((const u32 *)nullptr, (size_t)count * d.A); NEED(dc);
-    hipLaunchKernelGGL(k_root_counts, dim3(grid_for(count)), dim3(64 * WAVES_PER_BLOCK), 0, ctx->stream, d, (int)first, (int)count, dc);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(counts_out, dc, (size_t)count * d.A * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    u32 *dc = s.out(counts_out, (size_t)count * d.A);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_root_counts", k_root_counts, count, d, first, count, dc);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_game_status(rp_ctx *ctx, int32_t first, int32_t count, int32_t *phase_out, int32_t *sims_done_out, int32_t *moves_out,
@@ -5436,8 +5399,10 @@ extern "C" int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    int *dact = s.up(action, (size_t)count); NEED(dact);
-    DISPATCH_STAGED(ctx, k_advance, grid_for(count), d, (int)first, (int)count, (const int *)dact);
+    int *dact = s.in(action, (size_t)count);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_staged(ctx, "k_advance", GEO_KERNEL(ctx, false, k_advance<row_t>), count, d, first, count, dact);
+    if (rc != RP_OK) return rc;
     if (ended_out) HIPCHK(ctx, hipMemcpyAsync(ended_out, d.last_outcome + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (score_out) HIPCHK(ctx, hipMemcpyAsync(score_out, d.last_score + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return check_device_error(ctx);
@@ -5541,23 +5506,21 @@ static int generate_items_dev(rp_ctx *ctx, int64_t n, const uint32_t *seeds_host
     const DP &d = ctx->d;
     if (check_generator_rect(ctx, bin_w, bin_h) != RP_OK) return RP_ERR_ARG;
     Scratch s(ctx);
-    u32 *dseeds = s.up((const u32 *)seeds_host, (size_t)n); NEED(dseeds);
-    u32 *dmt = s.up((const u32 *)nullptr, (size_t)n * 624); NEED(dmt);
-    hipLaunchKernelGGL(k_items_generator, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (long long)n, d.N, bin_w, bin_h, (const u32 *)dseeds, dmt, out_dev);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // scratch is freed on return
-    return RP_OK;
+    u32 *dseeds = s.in((const u32 *)seeds_host, (size_t)n);
+    u32 *dmt = s.out((u32 *)nullptr, (size_t)n * 624);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch(ctx, "k_items_generator", k_items_generator, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, n, d.N, bin_w, bin_h, dseeds, dmt, out_dev);
+    return rc == RP_OK ? s.finish() : rc;  // scratch is freed on return
 }
 
 extern "C" int rp_generate_items(rp_ctx *ctx, int64_t n, const uint32_t *seeds, int32_t bin_w, int32_t bin_h, uint8_t *item_wh_out) {
     if (!ctx || n < 0 || !seeds || !item_wh_out) return fail(ctx, RP_ERR_ARG, "rp_generate_items: bad argument");
     if (n == 0) return RP_OK;
     Scratch s(ctx);
-    u8 *dout = s.up((const u8 *)nullptr, (size_t)n * ctx->d.N * 2); NEED(dout);
-    int rc = generate_items_dev(ctx, n, seeds, bin_w, bin_h, dout);
-    if (rc != RP_OK) return rc;
-    HIPCHK(ctx, hipMemcpy(item_wh_out, dout, (size_t)n * ctx->d.N * 2, hipMemcpyDeviceToHost));
-    return RP_OK;
+    u8 *dout = s.out(item_wh_out, (size_t)n * ctx->d.N * 2);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = generate_items_dev(ctx, n, seeds, bin_w, bin_h, dout);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_set_instance_pool_seeds(rp_ctx *ctx, int64_t n_instances, const uint32_t *seeds, int32_t bin_w, int32_t bin_h, uint64_t first_id) {
@@ -5644,8 +5607,8 @@ extern "C" int rp_begin_pool(rp_ctx *ctx) {
     if (!ctx) return RP_ERR_ARG;
     const DP &d = ctx->d;
     if (!ctx->pool.pd.wh) return fail(ctx, RP_ERR_STATE, "rp_begin_pool: no instance pool set");
-    DISPATCH_STAGED(ctx, k_pool_begin, grid_for(d.G), d);
-    return check_device_error(ctx);
+    const int rc = launch_staged(ctx, "k_pool_begin", GEO_KERNEL(ctx, false, k_pool_begin<row_t>), d.G, d);
+    return rc == RP_OK ? check_device_error(ctx) : rc;
 }
 
 extern "C" int rp_examples_count(rp_ctx *ctx, int64_t *n_out) {
@@ -5672,8 +5635,7 @@ extern "C" int rp_examples_tensors(rp_ctx *ctx, int64_t first, int64_t count, fl
     if (first + count > n) return fail(ctx, RP_ERR_ARG, "rp_examples_tensors: range [%lld,%lld) exceeds the %lld recorded examples", (long long)first, (long long)(first + count), (long long)n);
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
-    DISPATCH(ctx, k_examples, grid_for(count), d, own_examples(d), (long long)first, (long long)count, (const long long *)nullptr, planes_dev, pi_dev, value_dev);
-    return RP_OK;
+    return launch_waves(ctx, "k_examples", GEO_KERNEL(ctx, false, k_examples<row_t>), count, d, own_examples(d), first, count, nullptr, planes_dev, pi_dev, value_dev);
 }
 
 extern "C" int rp_examples_packed_count(rp_ctx *ctx, int64_t *n_examples_out, int64_t *n_sparse_out) {
@@ -5727,8 +5689,7 @@ extern "C" int rp_expand_examples(rp_ctx *ctx, int64_t n, const int64_t *index_d
     PackedEx ex;
     ex.key = key_dev; ex.wh = item_wh_dev; ex.value = value_dev; ex.sp_off64 = (const long long *)sp_off_dev; ex.sp_off32 = nullptr; ex.sp_n = sp_n_dev;
     ex.sp_act = sp_act_dev; ex.sp_cnt = sp_cnt_dev; ex.n_examples = n_examples; ex.n_sparse = n_sparse;
-    DISPATCH(ctx, k_examples, grid_for(n), ctx->d, ex, 0LL, (long long)n, (const long long *)index_dev, planes_dev, pi_dev, value_out_dev);
-    return RP_OK;
+    return launch_waves(ctx, "k_examples", GEO_KERNEL(ctx, false, k_examples<row_t>), n, ctx->d, ex, 0, n, (const long long *)index_dev, planes_dev, pi_dev, value_out_dev);
 }
 
 extern "C" int rp_check(rp_ctx *ctx) {
@@ -5758,8 +5719,8 @@ extern "C" int rp_examples_clear(rp_ctx *ctx) {
 
 extern "C" int rp_counters(rp_ctx *ctx, int64_t *out16, int32_t reset) {
     if (!ctx || !out16) return fail(ctx, RP_ERR_ARG, "rp_counters: bad argument");
-    hipLaunchKernelGGL(k_reduce_counters, dim3(1), dim3(1024), 0, ctx->stream, ctx->d);
-    HIPCHK(ctx, hipGetLastError());
+    const int rc = launch(ctx, "k_reduce_counters", k_reduce_counters, dim3(1), dim3(1024), 0, ctx->d);
+    if (rc != RP_OK) return rc;
     HIPCHK(ctx, hipMemcpyAsync(out16, ctx->d.counters, CNT_N * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     if (reset) HIPCHK(ctx, hipMemsetAsync(ctx->d.slot_cnt, 0, (size_t)ctx->d.G * CNT_N * sizeof(u64), ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -5778,8 +5739,8 @@ extern "C" int rp_arena_peak(rp_ctx *ctx, int32_t *prior_chunks_out, int32_t *vi
     if (!ctx || !prior_chunks_out || !visited_chunks_out) return fail(ctx, RP_ERR_ARG, "rp_arena_peak: bad argument");
     u32 pk[2] = {0, 0};
     u32 *tail = ctx->d.peak_chunks + (size_t)ctx->d.G * 2;
-    hipLaunchKernelGGL(k_reduce_peaks, dim3(1), dim3(256), 0, ctx->stream, ctx->d, tail);
-    HIPCHK(ctx, hipGetLastError());
+    const int rc = launch(ctx, "k_reduce_peaks", k_reduce_peaks, dim3(1), dim3(256), 0, ctx->d, tail);
+    if (rc != RP_OK) return rc;
     HIPCHK(ctx, hipMemcpyAsync(pk, tail, sizeof pk, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     *prior_chunks_out = (int)pk[0]; *visited_chunks_out = (int)pk[1];
@@ -5835,14 +5796,11 @@ extern "C" int rp_selftest_sqrt(rp_ctx *ctx, int64_t n, double *sqrt_n_out, doub
     if (!ctx || n < 0 || !sqrt_n_out || !sqrt_n_eps_out) return fail(ctx, RP_ERR_ARG, "rp_selftest_sqrt: bad argument");
     if (n == 0) return RP_OK;
     Scratch s(ctx);
-    double *a = s.up((const double *)nullptr, (size_t)n); NEED(a);
-    double *b = s.up((const double *)nullptr, (size_t)n); NEED(b);
-    hipLaunchKernelGGL(k_selftest_sqrt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long long)n, a, b);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(sqrt_n_out, a, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(sqrt_n_eps_out, b, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    double *a = s.out(sqrt_n_out, (size_t)n);
+    double *b = s.out(sqrt_n_eps_out, (size_t)n);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch(ctx, "k_selftest_sqrt", k_selftest_sqrt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, n, a, b);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_selftest_q_update(rp_ctx *ctx, int64_t n, const double *q, const uint8_t *q_kind, const uint32_t *nsa, const double *v,
@@ -5850,19 +5808,16 @@ extern "C" int rp_selftest_q_update(rp_ctx *ctx, int64_t n, const double *q, con
     if (!ctx || n < 0 || !q || !q_kind || !nsa || !v || !v_kind || !q_out || !q_kind_out) return fail(ctx, RP_ERR_ARG, "rp_selftest_q_update: bad argument");
     if (n == 0) return RP_OK;
     Scratch s(ctx);
-    double *dq = s.up(q, (size_t)n); NEED(dq);
-    u8 *dqk = s.up(q_kind, (size_t)n); NEED(dqk);
-    u32 *dn = s.up(nsa, (size_t)n); NEED(dn);
-    double *dv = s.up(v, (size_t)n); NEED(dv);
-    u8 *dvk = s.up(v_kind, (size_t)n); NEED(dvk);
-    double *dqo = s.up((const double *)nullptr, (size_t)n); NEED(dqo);
-    u8 *dqko = s.up((const u8 *)nullptr, (size_t)n); NEED(dqko);
-    hipLaunchKernelGGL(k_selftest_q, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long long)n, dq, dqk, dn, dv, dvk, dqo, dqko);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(q_out, dqo, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(q_kind_out, dqko, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    double *dq = s.in(q, (size_t)n);
+    u8 *dqk = s.in(q_kind, (size_t)n);
+    u32 *dn = s.in(nsa, (size_t)n);
+    double *dv = s.in(v, (size_t)n);
+    u8 *dvk = s.in(v_kind, (size_t)n);
+    double *dqo = s.out(q_out, (size_t)n);
+    u8 *dqko = s.out(q_kind_out, (size_t)n);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch(ctx, "k_selftest_q", k_selftest_q, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, n, dq, dqk, dn, dv, dvk, dqo, dqko);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_selftest_masked_prior(rp_ctx *ctx, int64_t B, const float *pi, const uint8_t *valid, double *p_out) {
@@ -5870,17 +5825,14 @@ extern "C" int rp_selftest_masked_prior(rp_ctx *ctx, int64_t B, const float *pi,
     if (B == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
-    float *dpi = s.up(pi, (size_t)B * d.A); NEED(dpi);
-    u8 *dva = s.up(valid, (size_t)B * d.A); NEED(dva);
-    double *dout = s.up((const double *)nullptr, (size_t)B * d.A); NEED(dout);
-    u16 *dact = s.up((const u16 *)nullptr, (size_t)B * d.A); NEED(dact);
-    float *dpc = s.up((const float *)nullptr, (size_t)B * d.A); NEED(dpc);
-    hipLaunchKernelGGL(k_selftest_prior, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), 0, ctx->stream, d, (long long)B, (const float *)dpi,
-                       (const u8 *)dva, dout, dact, dpc);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(p_out, dout, (size_t)B * d.A * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    float *dpi = s.in(pi, (size_t)B * d.A);
+    u8 *dva = s.in(valid, (size_t)B * d.A);
+    double *dout = s.out(p_out, (size_t)B * d.A);
+    u16 *dact = s.out((u16 *)nullptr, (size_t)B * d.A);  // the kernel's own scratch
+    float *dpc = s.out((float *)nullptr, (size_t)B * d.A);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_selftest_prior", k_selftest_prior, B, d, B, dpi, dva, dout, dact, dpc);
+    return rc == RP_OK ? s.finish() : rc;
 }
 
 extern "C" int rp_selftest_softmax(rp_ctx *ctx, int64_t B, const float *logits, int32_t wide, float *pi_out) {
@@ -5889,16 +5841,12 @@ extern "C" int rp_selftest_softmax(rp_ctx *ctx, int64_t B, const float *logits, 
     if (!wide && d.A > 1536) return fail(ctx, RP_ERR_ARG, "rp_selftest_softmax: the register form holds at most 1536 actions, not %d", d.A);
     if (B == 0) return RP_OK;
     Scratch s(ctx);
-    float *dx = s.up(logits, (size_t)B * d.A); NEED(dx);
-    float *dout = s.up((const float *)nullptr, (size_t)B * d.A); NEED(dout);
-    if (wide)  // one row of at most 8192 floats (the row 16-byte aligned like k_commit's): 32 KB, below the default limit
-        hipLaunchKernelGGL(k_selftest_softmax<1>, dim3((unsigned)B), dim3(64), (size_t)((d.A + 3) & ~3) * sizeof(float), ctx->stream, d.A, (long long)B,
-                           (const float *)dx, dout);
-    else  // WAVES_PER_BLOCK rows of at most 1536 floats
-        hipLaunchKernelGGL(k_selftest_softmax<0>, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), (size_t)WAVES_PER_BLOCK * d.A * sizeof(float), ctx->stream,
-                           d.A, (long long)B, (const float *)dx, dout);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(pi_out, dout, (size_t)B * d.A * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RP_OK;
+    float *dx = s.in(logits, (size_t)B * d.A);
+    float *dout = s.out(pi_out, (size_t)B * d.A);
+    int rc = s.ok();
+    if (rc == RP_OK && wide)  // one row of at most 8192 floats (the row 16-byte aligned like k_commit's): 32 KB, below the default limit
+        rc = launch(ctx, "k_selftest_softmax<1>", k_selftest_softmax<1>, dim3((unsigned)B), dim3(64), (size_t)((d.A + 3) & ~3) * sizeof(float), d.A, B, dx, dout);
+    else if (rc == RP_OK)  // WAVES_PER_BLOCK rows of at most 1536 floats
+        rc = launch(ctx, "k_selftest_softmax<0>", k_selftest_softmax<0>, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), (size_t)WAVES_PER_BLOCK * d.A * sizeof(float), d.A, B, dx, dout);
+    return rc == RP_OK ? s.finish() : rc;
 }

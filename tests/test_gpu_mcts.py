@@ -62,6 +62,8 @@ CASES = [  # W, H, N, sims, games, kind, rule
     (16, 16, 14, 60, 10, "peaked", "sample"),
     (40, 30, 60, 16, 4, "uniform", "argmax"),  # equal priors everywhere: every first visit takes the lowest unvisited action and rescans
     (24, 24, 40, 40, 6, "sparse", "sample"),   # zeros among the priors and the all-zero fallback on nodes with > 64 legal moves
+    # 8 192 actions, 64-bit rows, N > 64: the smallest board whose legal-move staging passes the default 64 KB of LDS (k_set_roots, k_search, k_moves)
+    (64, 4, 128, 6, 2, "hashed", "sample"),
 ]
 
 
@@ -231,6 +233,50 @@ def test_results_do_not_depend_on_slot_count_or_step_cap():
         actions, _, o, s = m.play_episode(sims, policy=1, seed=4242, episode_id=500 + g, want_counts=False)
         assert (runs[0][1][g], runs[0][2][g], runs[0][3][g]) == (o, s, len(actions))
         m.close()
+
+
+def test_staged_pool_and_advance_kernels_beyond_64k_lds():
+    """k_pool_begin and k_advance at 8 192 actions, where the legal-move staging passes the default 64 KB of LDS (the CASES row of
+    this board runs the other three staged kernels): (a) a pool's episodes and (b) an externally moved episode against the oracle."""
+    from resource_packing_self_play_amd import _lib
+    W, H, N, sims = 64, 4, 128, 6
+    A, salt, seed = W * N, 17, 777
+    rng = np.random.default_rng(64)
+    wh = np.stack([gen_items(rng, W, H, N) for _ in range(3)])
+    buf = rng.uniform(0.7, 1.0, 50)
+
+    def oracle():
+        return orc.OracleMCTS(W, H, N, 1.0, 0.75, lambda b, r: ev.table_eval("hashed", ev.pack_board(b), r, A, salt), lambda b, r: ev.tie_value(ev.pack_board(b), r, salt))
+
+    ids, outcome, score, moves, c = _play_pool(W, H, N, sims, wh, 2, 0, "hashed", salt, seed, buf)  # (a) k_pool_begin
+    assert list(ids) == [500, 501, 502]
+    stats = dict.fromkeys(("searches", "expansions", "nodes"), 0)
+    for g in range(3):
+        m = oracle()
+        m.begin_episode(wh[g, :, 0], wh[g, :, 1], W * H, buf)
+        actions, _, o, s = m.play_episode(sims, policy=1, seed=seed, episode_id=500 + g, want_counts=False)
+        assert (outcome[g], score[g], moves[g]) == (o, s, len(actions)), g
+        for k in stats:
+            stats[k] += m.stats()[k]
+        m.close()
+    assert (c["simulations"], c["expansions"], c["nodes"], c["episodes"]) == (stats["searches"], stats["expansions"], stats["nodes"], 3)
+
+    eng = make_engine(W, H, N, 1, sims, cpuct=1.0, alpha=0.75, move_rule=_lib.MOVE_EXTERNAL, tie_salt=salt)  # (b) k_advance
+    eng.set_rank_buffer(buf)
+    eng.begin_episodes(wh[:1], [W * H])
+    evaluate = host_evaluator(lambda s: "hashed", A, lambda s: salt)
+    played, ended = [], np.zeros(1, np.int32)
+    while ended[0] == 0 and len(played) <= N:
+        run_until_idle(eng, evaluate)
+        played.append(int(np.argmax(eng.root_counts()[0])))  # the first action with the highest count
+        ended, sc = eng.advance_roots(played[-1:])
+    m = oracle()
+    m.begin_episode(wh[0, :, 0], wh[0, :, 1], W * H, buf)
+    actions, _, o, s = m.play_episode(sims, policy=0, want_counts=False)
+    assert played == list(actions)
+    assert (ended[0], sc[0]) == (o, s)
+    assert_trees_equal(tree_as_dict(eng.dump_tree(0)), m.dump())
+    eng.close(); m.close()
 
 
 @pytest.mark.parametrize("cfg,W,H,N,sims,games,min_nodes", [("c3", 20, 20, 32, 400, 4, 3000), ("c4", 20, 20, 32, 100, 4, 800), ("c5", 50, 50, 128, 200, 1, 5000)])
