@@ -106,7 +106,7 @@ struct DP {  // device view of a context, passed by value to every kernel
     int reclaim;   // 1: a level's legal-move runs and visited blocks are recycled once the root has moved past it
     int pchunk, n_pchunks, vchunk, n_vchunks;  // level arenas: entries per chunk, chunks per slot
     int step_cap;  // max simulations a slot runs in one k_search launch (0 = until it needs the evaluator)
-    u32 magicW;  // a / W == (a * magicW) >> 20 for a < 8192
+    u32 magicW;  // a / W == (a * magicW) >> 20 for a < max(A, H * W + 64), checked in rp_create
     double cpuct;
     u64 seed, tie_salt;
     // per slot
@@ -4738,7 +4738,10 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     if (ctx->row64 && (d.KW & 1)) d.KW++;  // keep 64-bit rows 8-byte aligned
     d.magicW = (u32)(((1u << 20) + cfg->W - 1) / cfg->W);
     d.Hp = (cfg->H + 1) / 2; d.Wp = (cfg->W + 1) / 2;
-    for (u32 a = 0; a < 8192u; ++a)
+    // the kernels divide actions (a < A) and cell indices (below H * W rounded up to a whole wave).  Checking a fixed 8192 values refused
+    // W = 1, which the ABI allows: its magic is 2^20 and a * 2^20 leaves 32 bits from a = 4096 on, far above anything divided there
+    const u32 divided = (u32)std::max(d.A, cfg->H * cfg->W + 64);
+    for (u32 a = 0; a < divided; ++a)
         if (((a * d.magicW) >> 20) != a / (u32)cfg->W) return create_failed(ctx, fail(ctx, RP_ERR_ARG, "internal: division magic"));
     const size_t G = (size_t)d.G, N = (size_t)d.N;
     int rc = RP_OK;
