@@ -2877,6 +2877,25 @@ __device__ __forceinline__ void rs_conv(const float *img, __amdgpu_buffer_rsrc_t
     }
 }
 __device__ __forceinline__ f32x4 rs_relu(f32x4 v) { return (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)}; }
+// compile-time loop: f(integral_constant<int, 0>{}) ... f(integral_constant<int, N - 1>{})
+template <class F, int... I> __device__ __forceinline__ void pm_for_(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void pm_for(F &&f) { pm_for_(f, std::make_integer_sequence<int, N>{}); }
+// Row limit of every stage kernel: only the first *nrows_dev rows hold leaves (compact rows); without the pointer all B do.
+__device__ __forceinline__ long long stage_rows(long long B, const int *nrows_dev) {
+    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    return B;
+}
+// Who owns the LDS image a residual stage works on in place -- the one thing, beside the tiles a wave takes (tile0), in which the wave
+// and the workgroup form of a stage recipe (r32_stage) differ.  reads_done() stands between a convolution's last operand read and
+// the writes of its result over the image, writes_done() between those writes and the next convolution's reads.
+struct WaveImage {  // one wave: its LDS operations execute in order, so only the compiler has to be kept from moving the writes
+    static __device__ __forceinline__ void reads_done() {}
+    static __device__ __forceinline__ void writes_done() { lds_sync(); }
+};
+struct WgImage {  // the waves of a workgroup: every wave finishes its MFMA stream (barrier), then all waves write their tiles (barrier)
+    static __device__ __forceinline__ void reads_done() { lds_barrier(); }
+    static __device__ __forceinline__ void writes_done() { lds_barrier(); }
+};
 // Persistent waves: grid = as many workgroups as stay resident; a wave loops over tasks (IMGW leaves each).  Tables and zero borders
 // are set up once; the next task's x is staged into the image right behind this task's output stores and the x after that is
 // requested then, so it lands in registers during the four convolutions.  Nothing in the task loop branches on data: rows past the
@@ -2890,13 +2909,15 @@ __global__ void __launch_bounds__(256, RS_LB) k_resstage16(const float *__restri
     // the wave index as a scalar: everything derived from it (task numbers, buffer resources) is then provably wave-uniform; a
     // resource the compiler takes for divergent costs a waterfall loop around every buffer load and store
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }  // only the first *nrows_dev rows hold leaves (compact rows)
+    B = stage_rows(B, nrows_dev);
     if (((long long)blockIdx.x * 4) * IMGW >= B) return;
     const int PW = S_w + 2, PH = S_h + 2, PIX = S_h * S_w, IMG = PH * PW * RS_STRIDE, MP = IMGW * PIX, WAVE_F = IMGW * IMG + RS_STRIDE;
     constexpr int NTT = NT + (TAIL ? 1 : 0);  // table rows and LDS are sized for whole tiles
     int *ptab = (int *)rb_lds;  // [16 * NTT] LDS offset (within the wave's images) of channel 0 of pixel m of the wave's IMGW leaves
     float *img = rb_lds + 16 * NTT + (size_t)wv * WAVE_F;
     for (int i = threadIdx.x; i < 16 * NTT; i += blockDim.x) {
+        // spelled out here and in k_resstage16_wg: through a helper the fill is scheduled differently and k_resstage16<6, true> measures
+        // 0.5 - 0.7 % slower in three sessions (profiles/stage_recipe_ab.md)
         int im = i / PIX, pq = i - im * PIX, r = pq / S_w, c = pq - r * S_w;
         ptab[i] = i < MP ? im * IMG + ((r + 1) * PW + c + 1) * RS_STRIDE : 0;
     }
@@ -3136,6 +3157,57 @@ __device__ __forceinline__ void r32_conv(const float *img, __amdgpu_buffer_rsrc_
     f32x4 d0, d1[2], d2[2];
     r32_conv_t<NT, CIN, PS, false>(img, frs, fbase, fnext, PW, abase, acc, wq, 0, 0, 0, d0, d1, d2);
 }
+// Padded pixel index (in units of the pixel stride) of pixel m of consecutive images of PIX pixels, S_w wide, laid out in the geometry
+// above with IMGP = r32_imgp(S_h, S_w) padded pixels each.
+__device__ __forceinline__ int r32_pix(int m, int PIX, int S_w, int IMGP) {
+    const int im = m / PIX, pq = m - im * PIX, r = pq / S_w, c = pq - r * S_w;
+    return im * IMGP + (r + 1) * r32_pw(S_w) + c + 1;
+}
+// The four convolutions of a 32-channel residual stage over the NT tiles from tile0 of a task whose relu(x) stands in the image and whose
+// x is in xs: conv, bias + ReLU in place; conv, + skip x; conv, bias + ReLU; conv, + skip y1; the result leaves as 16-byte stores to
+// out + off (nbytes: the task's bytes, stores past them are dropped), relu(result) to out_relu + off if given.  sbias: the biases [4][32] in LDS;
+// abase[t] / pdst[t][mt]: where this lane reads the top-left tap of tile t's pixel and writes its channel quad 4 mt + g; rowoff: byte
+// offset of (pixel n, channel quad g) in a tile's 2 KB of [pixel][32] floats (taken from the kernel: derived again here it is not merged with the kernel's copy, one VGPR more in k_resstage32<5>).
+template <class IMG, int NT>
+__device__ __forceinline__ void r32_stage(float *img, const float *sbias, __amdgpu_buffer_rsrc_t frs, int PW, const int (&abase)[NT], const int (&pdst)[NT][2],
+                                          f32x4 (&xs)[NT][2], f32x4 (&wq)[3][2], int tile0, int rowoff, float *out, float *out_relu, size_t off, int nbytes) {
+    constexpr int CIN = 32, CONV_BYTES = 9 * CIN * 32 * 4;
+    const int g = lane_id() >> 4;
+    f32x4 acc[NT][2];
+    pm_for<4>([&](auto KC) {  // block 0 conv0, conv1 (+ skip x), block 1 conv0, conv1 (+ skip y1)
+        constexpr int kc = decltype(KC)::value;
+        IMG::writes_done();
+        r32_conv<NT, CIN>(img, frs, kc * CONV_BYTES, ((kc + 1) & 3) * CONV_BYTES, PW, abase, acc, wq);
+        if constexpr (kc < 3) IMG::reads_done();
+        const f32x4 ba = *(const f32x4 *)(sbias + 32 * kc + 4 * g), bb = *(const f32x4 *)(sbias + 32 * kc + 16 + 4 * g);
+        if constexpr (kc == 0 || kc == 2) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) { *(f32x4 *)(img + pdst[t][0]) = rs_relu(acc[t][0] + ba); *(f32x4 *)(img + pdst[t][1]) = rs_relu(acc[t][1] + bb); }
+        } else if constexpr (kc == 1) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                xs[t][0] = (acc[t][0] + ba) + xs[t][0]; xs[t][1] = (acc[t][1] + bb) + xs[t][1];  // y1, kept as block 1's skip operand
+                *(f32x4 *)(img + pdst[t][0]) = rs_relu(xs[t][0]); *(f32x4 *)(img + pdst[t][1]) = rs_relu(xs[t][1]);
+            }
+        } else {
+            const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + off), 0, nbytes, RS_BUF_FLAGS);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                acc[t][0] = (acc[t][0] + ba) + xs[t][0]; acc[t][1] = (acc[t][1] + bb) + xs[t][1];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][0]), ors, rowoff, (tile0 + t) * 2048, RS_STREAM_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][1]), ors, rowoff, (tile0 + t) * 2048 + 64, RS_STREAM_AUX);
+            }
+            if (out_relu != nullptr) {  // uniform: relu(result) for the flatten -> hidden_fc path
+                const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(out_relu + off), 0, nbytes, RS_BUF_FLAGS);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][0])), rrs, rowoff, (tile0 + t) * 2048, RS_STREAM_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][1])), rrs, rowoff, (tile0 + t) * 2048 + 64, RS_STREAM_AUX);
+                }
+            }
+        }
+    });
+}
 // frag = [4][9][2][2][64] float4, bias = [4][32] in execution order; IMGW leaves per wave, IMGW * PIX <= 16 * NT.  Persistent waves.
 template <int NT>
 __global__ void __launch_bounds__(256, 2) k_resstage32(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
@@ -3144,17 +3216,14 @@ __global__ void __launch_bounds__(256, 2) k_resstage32(const float *__restrict__
     constexpr int CIN = 32;
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if (((long long)blockIdx.x * 4) * IMGW >= B) return;
     constexpr int PS = r32_ps(CIN);
     const int PW = r32_pw(S_w), PIX = S_h * S_w, IMGP = r32_imgp(S_h, S_w), MP = IMGW * PIX, WAVE_P = IMGW * IMGP + 1;  // pixels per wave incl. the dummy
     int *ptab = (int *)rb_lds;     // [16 * NT] padded pixel index (within the wave's images) of pixel m of the wave's IMGW leaves
     float *sbias = rb_lds + 16 * NT;  // [4][32]
     float *img = sbias + 128 + (size_t)wv * WAVE_P * PS;
-    for (int i = threadIdx.x; i < 16 * NT; i += blockDim.x) {
-        int im = i / PIX, pq = i - im * PIX, r = pq / S_w, c = pq - r * S_w;
-        ptab[i] = i < MP ? im * IMGP + (r + 1) * PW + c + 1 : 0;
-    }
+    for (int i = threadIdx.x; i < 16 * NT; i += blockDim.x) ptab[i] = i < MP ? r32_pix(i, PIX, S_w, IMGP) : 0;
     for (int i = threadIdx.x; i < 128; i += blockDim.x) sbias[i] = bias[i];
     {
         float4 *z4 = (float4 *)img;
@@ -3174,7 +3243,6 @@ __global__ void __launch_bounds__(256, 2) k_resstage32(const float *__restrict__
         pdst[t][1] = pc * PS + 16 + 4 * g;    // quad 4 + g (channels 16 + 4 g ..) of this lane's pixel
     }
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)frag, 0, 4 * 9 * CIN * 32 * 4, RS_BUF_FLAGS);
-    constexpr int CONV_BYTES = 9 * CIN * 32 * 4;
     const int rowoff = n * 128 + g * 16;  // byte offset of (pixel n, channel quad g) in a tile's 2 KB of [pixel][32] floats; quad 4 + g: + 64
     auto task_bytes = [&](long long l0) { return (int)(B - l0 < IMGW ? B - l0 : IMGW) * PIX * 128; };
     f32x4 xv[NT][2], xs[NT][2], wq[3][2];
@@ -3195,54 +3263,7 @@ __global__ void __launch_bounds__(256, 2) k_resstage32(const float *__restrict__
     stage_x();
     if (leaf0 + stride_leaves < B) load_x(leaf0 + stride_leaves);
     for (; leaf0 < B; leaf0 += stride_leaves) {
-        const int nbytes = task_bytes(leaf0);
-        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)leaf0 * PIX * CIN), 0, nbytes, RS_BUF_FLAGS);
-        f32x4 acc[NT][2];
-#define R32_BIAS(k) const f32x4 ba = *(const f32x4 *)(sbias + 32 * (k) + 4 * g), bb = *(const f32x4 *)(sbias + 32 * (k) + 16 + 4 * g)
-        lds_sync();
-        r32_conv<NT, CIN>(img, frs, 0, CONV_BYTES, PW, abase, acc, wq);                     // block 0, conv0
-        {
-            R32_BIAS(0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) { *(f32x4 *)(img + pdst[t][0]) = rs_relu(acc[t][0] + ba); *(f32x4 *)(img + pdst[t][1]) = rs_relu(acc[t][1] + bb); }
-        }
-        lds_sync();
-        r32_conv<NT, CIN>(img, frs, CONV_BYTES, 2 * CONV_BYTES, PW, abase, acc, wq);        // block 0, conv1 (+ skip x)
-        {
-            R32_BIAS(1);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                xs[t][0] = (acc[t][0] + ba) + xs[t][0]; xs[t][1] = (acc[t][1] + bb) + xs[t][1];  // y1, kept as block 1's skip operand
-                *(f32x4 *)(img + pdst[t][0]) = rs_relu(xs[t][0]); *(f32x4 *)(img + pdst[t][1]) = rs_relu(xs[t][1]);
-            }
-        }
-        lds_sync();
-        r32_conv<NT, CIN>(img, frs, 2 * CONV_BYTES, 3 * CONV_BYTES, PW, abase, acc, wq);    // block 1, conv0
-        {
-            R32_BIAS(2);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) { *(f32x4 *)(img + pdst[t][0]) = rs_relu(acc[t][0] + ba); *(f32x4 *)(img + pdst[t][1]) = rs_relu(acc[t][1] + bb); }
-        }
-        lds_sync();
-        r32_conv<NT, CIN>(img, frs, 3 * CONV_BYTES, 0, PW, abase, acc, wq);                 // block 1, conv1 (+ skip y1)
-        {
-            R32_BIAS(3);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                acc[t][0] = (acc[t][0] + ba) + xs[t][0]; acc[t][1] = (acc[t][1] + bb) + xs[t][1];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][0]), ors, rowoff, t * 2048, RS_STREAM_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][1]), ors, rowoff, t * 2048 + 64, RS_STREAM_AUX);
-            }
-        }
-#undef R32_BIAS
-        if (out_relu != nullptr) {  // uniform: relu(result) for the flatten -> hidden_fc path
-            const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(out_relu + (size_t)leaf0 * PIX * CIN), 0, nbytes, RS_BUF_FLAGS);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][0])), rrs, rowoff, t * 2048, RS_STREAM_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][1])), rrs, rowoff, t * 2048 + 64, RS_STREAM_AUX);
-            }
-        }
+        r32_stage<WaveImage, NT>(img, sbias, frs, PW, abase, pdst, xs, wq, 0, rowoff, out, out_relu, (size_t)leaf0 * PIX * CIN, task_bytes(leaf0));
         if (leaf0 + stride_leaves < B) {
             stage_x();
             if (leaf0 + 2 * stride_leaves < B) load_x(leaf0 + 2 * stride_leaves);
@@ -3299,8 +3320,6 @@ template <int S, int ROLE> struct PmTab { static constexpr PmList L = pm_make_li
 static_assert(PmTab<3, 0>::L.n == 98 && PmTab<3, 0>::L.ok, "3x3: 49 (position, tap) pairs");
 static_assert(PmTab<5, 0>::L.n + PmTab<5, 1>::L.n + PmTab<5, 2>::L.n + PmTab<5, 3>::L.n == 2 * 169 && PmTab<5, 0>::L.np + PmTab<5, 1>::L.np + PmTab<5, 2>::L.np + PmTab<5, 3>::L.np == 25 &&
               PmTab<5, 0>::L.ok && PmTab<5, 1>::L.ok && PmTab<5, 2>::L.ok && PmTab<5, 3>::L.ok, "5x5: 169 pairs over four waves");
-template <class F, int... I> __device__ __forceinline__ void pm_for_(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void pm_for(F &&f) { pm_for_(f, std::make_integer_sequence<int, N>{}); }
 template <int S> __device__ __forceinline__ void pm_sync() {
     if constexpr (S == 3) lds_sync(); else lds_barrier();
 }
@@ -3406,7 +3425,7 @@ __global__ void __launch_bounds__(256, 2) k_resstage32_pm(const float *__restric
                                                           float *__restrict__ out, float *__restrict__ out_relu, long long B, const int *__restrict__ nrows_dev) {
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     float *sbias = rb_lds;  // [4][32]
     if constexpr (S == 3) {
         if ((long long)blockIdx.x * 64 >= B) return;
@@ -3618,7 +3637,7 @@ __global__ void __launch_bounds__(256, 2) k_resstage16_pp(const float *__restric
                                                           float *__restrict__ out, float *__restrict__ out_relu, long long B, const int *__restrict__ nrows_dev) {
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if ((long long)blockIdx.x * PP_LEAVES >= B) return;
     float *sbias = rb_lds;  // [4][16]
     for (int i = threadIdx.x; i < 64; i += blockDim.x) sbias[i] = bias[i];
@@ -3757,7 +3776,7 @@ __global__ void __launch_bounds__(256, 2) k_convpool32_pm(const float *__restric
                                                           float *__restrict__ out, long long B, const int *__restrict__ nrows_dev) {
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if ((long long)blockIdx.x * 16 >= B) return;
     const long long leaf0 = (long long)blockIdx.x * 16, stride = (long long)gridDim.x * 16;  // the same tasks for the four waves: uniform barriers
     switch (wv) {
@@ -3780,6 +3799,20 @@ __global__ void __launch_bounds__(256, 2) k_convpool32_pm(const float *__restric
 #ifdef CP_STAMP
 __device__ unsigned long long g_cp_stamp[8];
 #endif
+// Maximum over a 3x3 pooling window of pixels CP_PS floats apart.  row: this lane's channel quad of the window's centre; ou / od / ol /
+// orr: pixel offset of the upper / lower / left / right neighbour, 0 where it lies outside the image.  Branch-free: such a neighbour
+// reads the centre again (max with itself), so all nine 16-byte reads of a window are in flight together.
+__device__ __forceinline__ float4 cp_window_max(const float4 *row, int ou, int od, int ol, int orr) {
+    constexpr int Q = CP_PS / 4;
+    const float4 v0 = row[0], v1 = row[ol * Q], v2 = row[orr * Q], v3 = row[ou * Q], v4 = row[(ou + ol) * Q], v5 = row[(ou + orr) * Q],
+                 v6 = row[od * Q], v7 = row[(od + ol) * Q], v8 = row[(od + orr) * Q];
+    float4 m;
+    m.x = fmaxf(fmaxf(fmaxf(v0.x, v1.x), fmaxf(v2.x, v3.x)), fmaxf(fmaxf(v4.x, v5.x), fmaxf(fmaxf(v6.x, v7.x), v8.x)));
+    m.y = fmaxf(fmaxf(fmaxf(v0.y, v1.y), fmaxf(v2.y, v3.y)), fmaxf(fmaxf(v4.y, v5.y), fmaxf(fmaxf(v6.y, v7.y), v8.y)));
+    m.z = fmaxf(fmaxf(fmaxf(v0.z, v1.z), fmaxf(v2.z, v3.z)), fmaxf(fmaxf(v4.z, v5.z), fmaxf(fmaxf(v6.z, v7.z), v8.z)));
+    m.w = fmaxf(fmaxf(fmaxf(v0.w, v1.w), fmaxf(v2.w, v3.w)), fmaxf(fmaxf(v4.w, v5.w), fmaxf(fmaxf(v6.w, v7.w), v8.w)));
+    return m;
+}
 template <int NT, int CIN, bool TAIL = false>  // TAIL: NT tiles of 16 pixels + a tail of up to four (R32Tail)
 __global__ void __launch_bounds__(256, 2) k_convpool32(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
                                                        float *__restrict__ out, long long B, int S_h, int S_w, int IMGW, int wave_floats,
@@ -3788,7 +3821,7 @@ __global__ void __launch_bounds__(256, 2) k_convpool32(const float *__restrict__
     constexpr int PS = CP_PS;
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if (((long long)blockIdx.x * 4) * IMGW >= B) return;
     const int PW = r32_pw(S_w), PIX = S_h * S_w, IMGP = r32_imgp(S_h, S_w), MP = IMGW * PIX;
     const int Hp = (S_h + 1) >> 1, Wp = (S_w + 1) >> 1, PP = Hp * Wp;
@@ -3796,10 +3829,7 @@ __global__ void __launch_bounds__(256, 2) k_convpool32(const float *__restrict__
     int *ptab = (int *)rb_lds;            // [16 * NTT] padded pixel index of pixel m
     int *pool = ptab + 16 * NTT;          // [IMGW * PP]: padded index of the window's centre | up << 16 | down << 17 | left << 18 | right << 19
     float *img = rb_lds + 16 * NTT + ((IMGW * PP + 3) & ~3) + (size_t)wv * wave_floats;
-    for (int i = threadIdx.x; i < 16 * NTT; i += blockDim.x) {
-        int im = i / PIX, pq = i - im * PIX, r = pq / S_w, c = pq - r * S_w;
-        ptab[i] = i < MP ? im * IMGP + (r + 1) * PW + c + 1 : 0;
-    }
+    for (int i = threadIdx.x; i < 16 * NTT; i += blockDim.x) ptab[i] = i < MP ? r32_pix(i, PIX, S_w, IMGP) : 0;
     for (int i = threadIdx.x; i < IMGW * PP; i += blockDim.x) {
         int im = i / PP, pp = i - im * PP, pr = pp / Wp, px = pp - pr * Wp;
         pool[i] = (im * IMGP + (2 * pr + 1) * PW + 2 * px + 1) | ((pr > 0) << 16) | ((2 * pr + 1 < S_h) << 17) | ((px > 0) << 18) | ((2 * px + 1 < S_w) << 19);
@@ -3894,23 +3924,13 @@ __global__ void __launch_bounds__(256, 2) k_convpool32(const float *__restrict__
         }
         lds_sync();
         CP_T(2)
-        // pooling: 8 lanes x 4 channels per pooled pixel, window geometry from the workgroup's table.  Branch-free: a neighbour outside
-        // the image reads the centre again (max with itself), so all nine 16-byte reads of a window are in flight together
+        // pooling: 8 lanes x 4 channels per pooled pixel, window geometry from the workgroup's table
         float4 *o4 = (float4 *)(out + (size_t)leaf0 * PP * 32);
         for (int pq = lane >> 3; pq < nimg * PP; pq += 8) {
             const int info = pool[pq], ctr = info & 0xFFFF;
             const int up = (info >> 16) & 1, down = (info >> 17) & 1, left = (info >> 18) & 1, right = (info >> 19) & 1;
             const float4 *row = (const float4 *)(img + ctr * PS) + cq;
-            const int ou = up ? -PW : 0, od = down ? PW : 0, ol = left ? -1 : 0, orr = right ? 1 : 0;
-            constexpr int Q = PS / 4;
-            const float4 v0 = row[0], v1 = row[ol * Q], v2 = row[orr * Q], v3 = row[ou * Q], v4 = row[(ou + ol) * Q], v5 = row[(ou + orr) * Q],
-                         v6 = row[od * Q], v7 = row[(od + ol) * Q], v8 = row[(od + orr) * Q];
-            float4 m;
-            m.x = fmaxf(fmaxf(fmaxf(v0.x, v1.x), fmaxf(v2.x, v3.x)), fmaxf(fmaxf(v4.x, v5.x), fmaxf(fmaxf(v6.x, v7.x), v8.x)));
-            m.y = fmaxf(fmaxf(fmaxf(v0.y, v1.y), fmaxf(v2.y, v3.y)), fmaxf(fmaxf(v4.y, v5.y), fmaxf(fmaxf(v6.y, v7.y), v8.y)));
-            m.z = fmaxf(fmaxf(fmaxf(v0.z, v1.z), fmaxf(v2.z, v3.z)), fmaxf(fmaxf(v4.z, v5.z), fmaxf(fmaxf(v6.z, v7.z), v8.z)));
-            m.w = fmaxf(fmaxf(fmaxf(v0.w, v1.w), fmaxf(v2.w, v3.w)), fmaxf(fmaxf(v4.w, v5.w), fmaxf(fmaxf(v6.w, v7.w), v8.w)));
-            o4[pq * 8 + cq] = m;
+            o4[pq * 8 + cq] = cp_window_max(row, up ? -PW : 0, down ? PW : 0, left ? -1 : 0, right ? 1 : 0);
         }
         CP_T(3)
         lds_sync();  // the windows have been read: the next task's x may overwrite the interior pixels
@@ -3936,8 +3956,9 @@ extern "C" int rp_debug_cp_stamp(unsigned long long *host8, int reset) {  // dia
 // (accumulators and skip operands stay in registers as above, NT per wave instead of per image; eight waves keep NT <= 5 for 40 tiles
 // and put two waves on every SIMD, so one wave's barrier wait is another's MFMA time).  A convolution reads the whole image and its output
 // overwrites it IN PLACE: every wave finishes its MFMA stream (barrier), then all waves write their tiles (barrier).  The MFMA
-// streams, fragment orders and epilogue arithmetic are the wave kernels' (rs_conv / r32_conv): same float32 operations in the same
-// order per pixel, so the results are bit-identical to them on images both can take.
+// streams, fragment orders and epilogue arithmetic are the wave kernels' (rs_conv / r32_conv; the 32-channel recipe is ONE function for
+// both forms, r32_stage<WaveImage | WgImage>): same float32 operations in the same order per pixel, so the results are bit-identical to
+// them on images both can take.
 // ------------------------------------------------------------------------------------------------
 template <int NT, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES) k_resstage16_wg(const float *__restrict__ x, const float *__restrict__ frag, const float *__restrict__ bias,
@@ -3945,7 +3966,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_resstage16_wg(const float *__res
                                                           const int *__restrict__ nrows_dev) {
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if ((long long)blockIdx.x >= B) return;
     const int PW = S_w + 2, PH = S_h + 2, PIX = S_h * S_w, IMG = PH * PW * RS_STRIDE;
     float *img = rb_lds;  // [IMG] + one dummy pixel
@@ -4014,7 +4035,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_resstage32_wg(const float *__res
     constexpr int CIN = 32;
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if ((long long)blockIdx.x * IMGW >= B) return;
     constexpr int PS = r32_ps(CIN);
     const int PW = r32_pw(S_w), PIX = S_h * S_w, IMGP = r32_imgp(S_h, S_w), MP = IMGW * PIX, WG_P = IMGW * IMGP + 1;  // pixels incl. the dummy
@@ -4029,14 +4050,12 @@ __global__ void __launch_bounds__(64 * WAVES) k_resstage32_wg(const float *__res
     int abase[NT], pdst[NT][2];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const int m = (wv * NT + t) * 16 + n, mm = m < MP ? m : 0, im = mm / PIX, pq = mm - im * PIX, r = pq / S_w, c = pq - r * S_w;
-        const int pix = im * IMGP + (r + 1) * PW + c + 1, pc = m < MP ? pix : IMGW * IMGP;
+        const int m = (wv * NT + t) * 16 + n, pix = r32_pix(m < MP ? m : 0, PIX, S_w, IMGP), pc = m < MP ? pix : IMGW * IMGP;
         abase[t] = (pix - (PW + 1)) * PS + 8 * g;
         pdst[t][0] = pc * PS + 4 * g;
         pdst[t][1] = pc * PS + 16 + 4 * g;
     }
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)frag, 0, 4 * 9 * CIN * 32 * 4, RS_BUF_FLAGS);
-    constexpr int CONV_BYTES = 9 * CIN * 32 * 4;
     const int rowoff = n * 128 + g * 16, tile0 = wv * NT;
     f32x4 xs[NT][2], wq[3][2];
     wq[0][0] = rs_load_b(frs, lane * 16, 0); wq[0][1] = rs_load_b(frs, lane * 16, 1024);
@@ -4046,7 +4065,6 @@ __global__ void __launch_bounds__(64 * WAVES) k_resstage32_wg(const float *__res
     for (long long leaf0 = (long long)blockIdx.x * IMGW; leaf0 < B; leaf0 += stride_leaves) {
         const int nbytes = (int)(B - leaf0 < IMGW ? B - leaf0 : IMGW) * PIX * 128;
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(x + (size_t)leaf0 * PIX * CIN), 0, nbytes, RS_BUF_FLAGS);
-        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)leaf0 * PIX * CIN), 0, nbytes, RS_BUF_FLAGS);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -4054,55 +4072,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_resstage32_wg(const float *__res
                 xs[t][mt] = rs_load_x(xrs, rowoff, (tile0 + t) * 2048 + 64 * mt);
                 *(f32x4 *)(img + pdst[t][mt]) = rs_relu(xs[t][mt]);
             }
-        f32x4 acc[NT][2];
-#define R32_BIAS(k) const f32x4 ba = *(const f32x4 *)(sbias + 32 * (k) + 4 * g), bb = *(const f32x4 *)(sbias + 32 * (k) + 16 + 4 * g)
-        lds_barrier();
-        r32_conv<NT, CIN>(img, frs, 0, CONV_BYTES, PW, abase, acc, wq);
-        lds_barrier();
-        {
-            R32_BIAS(0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) { *(f32x4 *)(img + pdst[t][0]) = rs_relu(acc[t][0] + ba); *(f32x4 *)(img + pdst[t][1]) = rs_relu(acc[t][1] + bb); }
-        }
-        lds_barrier();
-        r32_conv<NT, CIN>(img, frs, CONV_BYTES, 2 * CONV_BYTES, PW, abase, acc, wq);
-        lds_barrier();
-        {
-            R32_BIAS(1);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                xs[t][0] = (acc[t][0] + ba) + xs[t][0]; xs[t][1] = (acc[t][1] + bb) + xs[t][1];
-                *(f32x4 *)(img + pdst[t][0]) = rs_relu(xs[t][0]); *(f32x4 *)(img + pdst[t][1]) = rs_relu(xs[t][1]);
-            }
-        }
-        lds_barrier();
-        r32_conv<NT, CIN>(img, frs, 2 * CONV_BYTES, 3 * CONV_BYTES, PW, abase, acc, wq);
-        lds_barrier();
-        {
-            R32_BIAS(2);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) { *(f32x4 *)(img + pdst[t][0]) = rs_relu(acc[t][0] + ba); *(f32x4 *)(img + pdst[t][1]) = rs_relu(acc[t][1] + bb); }
-        }
-        lds_barrier();
-        r32_conv<NT, CIN>(img, frs, 3 * CONV_BYTES, 0, PW, abase, acc, wq);
-        {
-            R32_BIAS(3);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                acc[t][0] = (acc[t][0] + ba) + xs[t][0]; acc[t][1] = (acc[t][1] + bb) + xs[t][1];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][0]), ors, rowoff, (tile0 + t) * 2048, RS_STREAM_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t][1]), ors, rowoff, (tile0 + t) * 2048 + 64, RS_STREAM_AUX);
-            }
-        }
-#undef R32_BIAS
-        if (out_relu != nullptr) {
-            const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(out_relu + (size_t)leaf0 * PIX * CIN), 0, nbytes, RS_BUF_FLAGS);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][0])), rrs, rowoff, (tile0 + t) * 2048, RS_STREAM_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rs_relu(acc[t][1])), rrs, rowoff, (tile0 + t) * 2048 + 64, RS_STREAM_AUX);
-            }
-        }
+        r32_stage<WgImage, NT>(img, sbias, frs, PW, abase, pdst, xs, wq, tile0, rowoff, out, out_relu, (size_t)leaf0 * PIX * CIN, nbytes);
         lds_barrier();
     }
 }
@@ -4116,7 +4086,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_convpool32_wg(const float *__res
     constexpr int XQ = CIN / 16;
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int lane = lane_id(), wv = wave_in_block();
-    if (nrows_dev) { const long long n = *nrows_dev; if (n < B) B = n; }
+    B = stage_rows(B, nrows_dev);
     if ((long long)blockIdx.x * IMGW >= B) return;
     constexpr int PS = r32_ps(CIN);
     const int PW = r32_pw(S_w), PIX = S_h * S_w, IMGP = r32_imgp(S_h, S_w), MP = IMGW * PIX;
@@ -4130,6 +4100,8 @@ __global__ void __launch_bounds__(64 * WAVES) k_convpool32_wg(const float *__res
     int abase[NT], pin[NT][XQ], m_row[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
+        // r32_pix() spelled out: through the helper every instantiation of this kernel takes 3 to 6 more VGPRs and <3, CIN, 4> loses a
+        // wave per SIMD (profiles/stage_recipe_static.md)
         const int m = (wv * NT + t) * 16 + n, mm = m < MP ? m : 0, im = mm / PIX, pq = mm - im * PIX, r = pq / S_w, c = pq - r * S_w;
         const int pix = im * IMGP + (r + 1) * PW + c + 1, pc = m < MP ? pix : IMGW * IMGP;
         abase[t] = (pix - (PW + 1)) * PS + CIN / 4 * g;
@@ -4160,24 +4132,16 @@ __global__ void __launch_bounds__(64 * WAVES) k_convpool32_wg(const float *__res
 #pragma unroll
         for (int t = 0; t < NT; ++t)
             if (m_row[t] < 16 * ((MP + 15) / 16)) {  // rows past the last (partly filled) tile would land beyond the staging area
-                *(f32x4 *)(img + m_row[t] * 36 + 4 * g) = acc[t][0] + ba;
-                *(f32x4 *)(img + m_row[t] * 36 + 16 + 4 * g) = acc[t][1] + bb;
+                *(f32x4 *)(img + m_row[t] * CP_PS + 4 * g) = acc[t][0] + ba;
+                *(f32x4 *)(img + m_row[t] * CP_PS + 16 + 4 * g) = acc[t][1] + bb;
             }
         lds_barrier();
         float4 *o4 = (float4 *)(out + (size_t)leaf0 * PP * 32);
         for (int pq = threadIdx.x >> 3; pq < nimg * PP; pq += 8 * WAVES) {
             const int im = pq / PP, pp = pq - im * PP, pr = pp / Wp, px = pp - pr * Wp;
             const int ctr = im * PIX + 2 * pr * S_w + 2 * px;
-            const int ou = pr > 0 ? -S_w : 0, od = 2 * pr + 1 < S_h ? S_w : 0, ol = px > 0 ? -1 : 0, orr = 2 * px + 1 < S_w ? 1 : 0;
-            const float4 *row = (const float4 *)(img + ctr * 36) + cq;
-            const float4 v0 = row[0], v1 = row[ol * 9], v2 = row[orr * 9], v3 = row[ou * 9], v4 = row[(ou + ol) * 9], v5 = row[(ou + orr) * 9],
-                         v6 = row[od * 9], v7 = row[(od + ol) * 9], v8 = row[(od + orr) * 9];
-            float4 m;
-            m.x = fmaxf(fmaxf(fmaxf(v0.x, v1.x), fmaxf(v2.x, v3.x)), fmaxf(fmaxf(v4.x, v5.x), fmaxf(fmaxf(v6.x, v7.x), v8.x)));
-            m.y = fmaxf(fmaxf(fmaxf(v0.y, v1.y), fmaxf(v2.y, v3.y)), fmaxf(fmaxf(v4.y, v5.y), fmaxf(fmaxf(v6.y, v7.y), v8.y)));
-            m.z = fmaxf(fmaxf(fmaxf(v0.z, v1.z), fmaxf(v2.z, v3.z)), fmaxf(fmaxf(v4.z, v5.z), fmaxf(fmaxf(v6.z, v7.z), v8.z)));
-            m.w = fmaxf(fmaxf(fmaxf(v0.w, v1.w), fmaxf(v2.w, v3.w)), fmaxf(fmaxf(v4.w, v5.w), fmaxf(fmaxf(v6.w, v7.w), v8.w)));
-            o4[pq * 8 + cq] = m;
+            const float4 *row = (const float4 *)(img + ctr * CP_PS) + cq;
+            o4[pq * 8 + cq] = cp_window_max(row, pr > 0 ? -S_w : 0, 2 * pr + 1 < S_h ? S_w : 0, px > 0 ? -1 : 0, 2 * px + 1 < S_w ? 1 : 0);
         }
         lds_barrier();
         if (leaf0 + stride_leaves < B) {  // the staging copy overwrote the padded images: borders back to zero for the next task
