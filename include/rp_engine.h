@@ -33,12 +33,13 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 9  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
+#define RP_ABI_VERSION 10  /* 4: sparse replay buffer (rp_config.max_sparse, rp_examples_packed*, rp_expand_examples), rp_leaf_count_async
                              5: placement trace (rp_set_trace, rp_pop_finished_packings)
                              6: softmax in the commit kernel for every action space (rp_commit_eval_logits_wide, rp_debug_commit_plan)
                              7: the commit kernel's softmax as a self-test (rp_selftest_softmax)
                              8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states)
-                             9: initial states of pool instances (rp_set_instance_initial) */
+                             9: initial states of pool instances (rp_set_instance_initial)
+                             10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -160,7 +161,8 @@ int rp_set_instance_initial(rp_ctx *ctx, int64_t n, const uint64_t *rows /*[n][H
  * the threshold sorted[int(floor(len*alpha))-1] is recomputed and used by every slot from now on. */
 int rp_set_rank_buffer(rp_ctx *ctx, const double *rewards, int32_t n);
 /* Re-root slot(s) at an arbitrary state without clearing the tree (MCTS.getActionProb called with a
- * new canonicalBoard on the same MCTS object, CoachBPP.py:74-78). */
+ * new canonicalBoard on the same MCTS object, CoachBPP.py:74-78).  RP_ERR_STATE while incumbents are on (rp_set_incumbent): the engine
+ * does not know the moves that lead to the new root, so it could not say how an incumbent found from there is reached. */
 int rp_set_roots(rp_ctx *ctx, int32_t first, int32_t count, const uint64_t *rows /*[count][H]*/,
                  const uint8_t *remaining /*[count][N]*/);
 
@@ -192,6 +194,26 @@ int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples);
  * the kernels take one uniform branch.  Kernel arguments are baked into captured graphs: re-capture after switching, as after
  * rp_set_move_rule.  Records of episodes that finished while the trace was off carry no trace: drain the ring before switching. */
 int rp_set_trace(rp_ctx *ctx, int32_t enable);
+/* Incumbents: with enable != 0 every episode of a slot carries the best complete packing its search saw.  The search fills Es once per
+ * state, when it first meets it (MCTS_bpp.py:78-83), and a state without a legal move is scored there by getRankedReward
+ * (BinPackingGame.py:188-212); the reference keeps the sign only.  The incumbent is defined over the terminal states MATERIALISED in the
+ * slot's tree during the episode, in creation order -- by a simulation of rp_search_step, by a played move whose child did not exist
+ * yet (any rp_move_rule, rp_advance_roots included), by the episode's initial state when it is terminal, by rp_begin_episodes: a new
+ * terminal with score r replaces the incumbent iff r is strictly greater, and an episode starts without one, so the first terminal
+ * always enters (even with r == 0) and the first created among equals stays.  The record: score (that r), outcome (the node's Es, the
+ * r == bl tie resolved as the search resolves it), moves, action[moves] from the episode's initial state = the moves played so far
+ * followed by the creating simulation's path, prefix (the number of played moves when it was found), board (the terminal's H row masks)
+ * and updates (how often the incumbent was replaced in this episode, the first entry included).  Every finished episode has one -- its
+ * own final state was materialised -- so best score >= played score always.  The record is a function of the search alone: not of
+ * rp_set_step_cap, rp_set_compact_rows, the slot, or graph replay.  Playouts of rp_rollout_eval do NOT feed it: tree terminals only.
+ * Refused with RP_ERR_STATE while any slot is in the middle of an episode.  The buffers are allocated on the first enable:
+ * (G + fin_cap) * S + 16 G bytes, S = 24 + 8 H + 4 N rounded up to a multiple of 8 and fin_cap = max(4 G, 1024) -- 52 MB at 32 768 slots
+ * of 20x20 / 32 items in two contexts; with incumbents off nothing is allocated and every hook is one uniform branch.  While they are
+ * on, rp_search_step launches one more small kernel, and a slot's launch ends with the simulation that brought a terminal into its tree
+ * (it goes on in the next one, as under rp_set_step_cap: scheduling only).  Kernel arguments are baked into captured graphs: re-capture
+ * after switching.  Records of episodes that finished while incumbents were off carry none: drain the ring before switching.
+ * rp_set_roots is refused while they are on. */
+int rp_set_incumbent(rp_ctx *ctx, int32_t enable);
 /* Changes args.numMCTSSims for the following searches (MCTS_bpp.py:37); rp_search_step stops a slot after this many
  * simulations from its current root. */
 int rp_set_sims(rp_ctx *ctx, int32_t sims);
@@ -330,6 +352,20 @@ int rp_pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_
 int rp_pop_finished_packings(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
                              int32_t *moves_out, uint16_t *action_out /*[max_n][N]*/, uint64_t *rows_out /*[max_n][N]*/,
                              uint64_t *board_out /*[max_n][H]*/, int64_t *n_out);
+/* rp_pop_finished_packings plus each episode's incumbent (rp_set_incumbent: the terminals of MCTS_bpp.py:78-83, scored by
+ * BinPackingGame.py:188-212): best_action_out[k][m] is move m of record k's incumbent from the episode's initial state (zero for
+ * m >= best_moves_out[k]), best_board_out[k][r] row r of its bin.  Same ring and cursor as rp_pop_finished; any output may be NULL.
+ * RP_ERR_ARG while incumbents are off, and when action_out / rows_out / board_out is requested while the trace is off. */
+int rp_pop_finished_best(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out, int32_t *moves_out,
+                         uint16_t *action_out /*[max_n][N]*/, uint64_t *rows_out /*[max_n][N]*/, uint64_t *board_out /*[max_n][H]*/,
+                         double *best_score_out, int32_t *best_outcome_out, int32_t *best_moves_out, int32_t *best_prefix_out,
+                         int32_t *best_updates_out, uint16_t *best_action_out /*[max_n][N]*/, uint64_t *best_board_out /*[max_n][H]*/,
+                         int64_t *n_out);
+/* Running incumbents of slots first .. first + count - 1 as host copies (the Es terminals of MCTS_bpp.py:78-83 seen so far in each
+ * slot's episode, scored by BinPackingGame.py:188-212): moves_out = -1, and zeros elsewhere, where the episode has none yet.  Any output
+ * may be NULL.  RP_ERR_ARG while incumbents are off. */
+int rp_incumbents(rp_ctx *ctx, int32_t first, int32_t count, double *score_out, int32_t *outcome_out, int32_t *moves_out,
+                  int32_t *prefix_out, int32_t *updates_out, uint16_t *action_out /*[count][N]*/, uint64_t *board_out /*[count][H]*/);
 /* Engine counters summed over slots since create/reset: [0] simulations, [1] expansions (leaf evaluations),
  * [2] terminal returns, [3] path edges walked, [4] sum of n_valid at selected nodes, [5] sum of n_valid at
  * expanded leaves, [6] transposition links, [7] nodes created, [8] moves played, [9] episodes finished,

@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RP_ENGINE_LIB: another build of the same library (kernel experiments with different compile-time settings); must exist
 LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_engine.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
@@ -63,6 +63,8 @@ _SIGS = {
     "rp_set_move_rule": (C.c_int, [_vp, _i32, _i32]),
     "rp_set_sims": (C.c_int, [_vp, _i32]),
     "rp_set_trace": (C.c_int, [_vp, _i32]),
+    "rp_set_incumbent": (C.c_int, [_vp, _i32]),
+    "rp_incumbents": (C.c_int, [_vp, _i32, _i32] + [_vp] * 7),
     "rp_last_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_search_step": (C.c_int, [_vp, _vp]),
     "rp_leaf_planes": (C.c_int, [_vp, _vp, _i64]),
@@ -90,6 +92,7 @@ _SIGS = {
     "rp_advance_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "rp_pop_finished": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "rp_pop_finished_packings": (C.c_int, [_vp, _i64] + [_vp] * 8),
+    "rp_pop_finished_best": (C.c_int, [_vp, _i64] + [_vp] * 15),
     "rp_counters": (C.c_int, [_vp, _vp, _i32]),
     "rp_examples_count": (C.c_int, [_vp, _vp]),
     "rp_examples_tensors": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
@@ -181,6 +184,7 @@ class Engine:
         self.h = h
         self.pool_size = 0  # size of the pool set last (rp_set_instance_pool*)
         self.trace = False  # placement trace (set_trace)
+        self.incumbent = False  # incumbents (set_incumbent)
 
     def close(self):
         if getattr(self, "h", None):
@@ -310,6 +314,22 @@ class Engine:
         """Placement trace (rp_set_trace): every move's (action, filled rows) and the final bin, read with pop_finished(packings=True)."""
         self._ck(self.L.rp_set_trace(self.h, 1 if on else 0))
         self.trace = bool(on)
+
+    def set_incumbent(self, on=True):
+        """Incumbents (rp_set_incumbent): per episode the best terminal state its search tree saw, the first created among equals; read
+        with pop_finished(best=True) and incumbents().  Refused while a slot is in mid-episode; re-capture graphs after switching."""
+        self._ck(self.L.rp_set_incumbent(self.h, 1 if on else 0))
+        self.incumbent = bool(on)
+
+    def incumbents(self, first=0, count=None):
+        """Running incumbents of slots first .. first + count - 1 (rp_incumbents) -> dict of score f64 [n], outcome / moves / prefix /
+        updates i32 [n], action u16 [n, N] (zero past moves) and board u64 [n, H]; moves = -1 where the episode has none yet."""
+        count = self.G - first if count is None else count
+        d = dict(score=np.zeros(count, np.float64), outcome=np.zeros(count, np.int32), moves=np.zeros(count, np.int32),
+                 prefix=np.zeros(count, np.int32), updates=np.zeros(count, np.int32), action=np.zeros((count, self.N), np.uint16),
+                 board=np.zeros((count, self.H), np.uint64))
+        self._ck(self.L.rp_incumbents(self.h, first, count, *[_ptr(d[k]) for k in ("score", "outcome", "moves", "prefix", "updates", "action", "board")]))
+        return d
 
     def last_values(self, first=0, count=None):
         count = self.G - first if count is None else count
@@ -611,13 +631,29 @@ class Engine:
         self._ck(self.L.rp_advance_roots(self.h, first, count, _ptr(action), _ptr(ended), _ptr(score)))
         return ended, score
 
-    def pop_finished(self, max_n=None, packings=False):
+    def pop_finished(self, max_n=None, packings=False, best=False):
         """(episode ids, outcomes, scores, moves) of up to max_n finished episodes, oldest first; packings=True adds each one's
-        placement trace: actions u16 [n, N], filled-row masks u64 [n, N] and final bin rows u64 [n, H] (rp_pop_finished_packings)."""
+        placement trace: actions u16 [n, N], filled-row masks u64 [n, N] and final bin rows u64 [n, H] (rp_pop_finished_packings);
+        best=True adds, last, a dict with each one's incumbent (rp_pop_finished_best): score f64 [n], outcome / moves / prefix / updates
+        i32 [n], action u16 [n, N] (zero past moves) and board u64 [n, H]."""
         if max_n is None:  # the ring holds at most max(4 G, 1024) records
-            max_n = max(4 * self.G, 1024) if packings else 1 << 20
+            max_n = max(4 * self.G, 1024) if packings or best else 1 << 20
         ids = np.empty(max_n, np.uint64); oc = np.empty(max_n, np.int32); sc = np.empty(max_n, np.float64); mv = np.empty(max_n, np.int32)
         n = _i64(0)
+        if best:
+            act = rows = board = None
+            if packings:
+                act = np.empty((max_n, self.N), np.uint16); rows = np.empty((max_n, self.N), np.uint64); board = np.empty((max_n, self.H), np.uint64)
+            b = dict(score=np.empty(max_n, np.float64), outcome=np.empty(max_n, np.int32), moves=np.empty(max_n, np.int32),
+                     prefix=np.empty(max_n, np.int32), updates=np.empty(max_n, np.int32), action=np.empty((max_n, self.N), np.uint16),
+                     board=np.empty((max_n, self.H), np.uint64))
+            self._ck(self.L.rp_pop_finished_best(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), _ptr(act), _ptr(rows), _ptr(board),
+                                                 *[_ptr(b[k]) for k in ("score", "outcome", "moves", "prefix", "updates", "action", "board")], C.byref(n)))
+            k = n.value
+            b = {key: val[:k].copy() for key, val in b.items()}
+            if packings:
+                return ids[:k], oc[:k], sc[:k], mv[:k], act[:k].copy(), rows[:k].copy(), board[:k].copy(), b
+            return ids[:k], oc[:k], sc[:k], mv[:k], b
         if not packings:
             self._ck(self.L.rp_pop_finished(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), C.byref(n)))
             k = n.value

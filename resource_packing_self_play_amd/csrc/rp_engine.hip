@@ -101,6 +101,12 @@ struct VisEntry {
     u32 idx;     // index into the node's legal-move run
     u32 pad;
 };
+// A terminal node that k_search created, with its score r, on its way to k_incumbent.
+struct IncNew {
+    double r;
+    u32 node;  // NONE32: none pending
+    u32 pad;
+};
 struct DP {  // device view of a context, passed by value to every kernel
     int W, H, N, A, G, sims, node_cap, edge_cap, vis_cap, table_cap, KW, RW, RMW, move_rule;
     int reclaim;   // 1: a level's legal-move runs and visited blocks are recycled once the root has moved past it
@@ -192,6 +198,13 @@ struct DP {  // device view of a context, passed by value to every kernel
     u16 *fin_tr_action;  // [fin_cap][N], zero past the episode's moves
     u64 *fin_tr_rows;    // [fin_cap][N]
     u64 *fin_board;      // [fin_cap][H] row masks of the final bin
+    // incumbents (rp_set_incumbent): the best terminal state materialised in the slot's tree during its episode, the first created among
+    // equals.  One record of inc_stride bytes per slot and per ring entry (IncRec below: ONE base address per hook, the search kernel has
+    // no scalar registers to spare).  inc == NULL while it is off: every hook is then one wave-uniform branch.
+    u8 *inc;       // [G] running episodes
+    u8 *fin_inc;   // [fin_cap] finished episodes, at the ring index of their record
+    int inc_stride;
+    IncNew *inc_new;  // [G] k_search's new terminal, not offered yet
 };
 // the first error of a launch sequence is the one reported (later ones are usually its consequences)
 __device__ __forceinline__ void set_error(const DP &p, int code) { atomicCAS(p.error, 0, code); }
@@ -530,6 +543,21 @@ template <typename T> __device__ __host__ __forceinline__ T *slot_region(const D
     return (T *)((u8 *)slot0 + (size_t)g * p.slab_stride);
 }
 
+// An incumbent record (DP::inc, DP::fin_inc): score f64 | outcome, moves (-1: none yet), prefix, updates i32 | board u64 [H] | action
+// u16 [N] (entries past `moves` are stale in a running record, zero in the ring) | the moves played so far in the episode u16 [N];
+// rounded up to 8 bytes.
+struct IncRec {
+    u8 *b;
+    int H, N;
+    __host__ __device__ IncRec(u8 *b_, int H_, int N_) : b(b_), H(H_), N(N_) {}
+    __host__ __device__ double *score() const { return (double *)b; }
+    __host__ __device__ int *meta() const { return (int *)(b + 8); }
+    __host__ __device__ u64 *board() const { return (u64 *)(b + 24); }
+    __host__ __device__ u16 *action() const { return (u16 *)(b + 24 + 8 * (size_t)H); }
+    __host__ __device__ u16 *played() const { return action() + N; }
+    static __host__ __device__ size_t stride(int H, int N) { return (24 + 8 * (size_t)H + 4 * (size_t)N + 7) & ~(size_t)7; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // slot-local tree
 // ------------------------------------------------------------------------------------------------
@@ -546,7 +574,8 @@ template <typename row_t, bool BIG = true> struct Tree {
     Arena pa, va;  // legal-move runs, visited blocks
     u32 n_nodes;
     u32 cnt = 0;   // per-launch event counts: LANE k holds counter k (one VGPR; sixteen wave-uniform counters took sixteen SGPRs of a
-                   // kernel that already spills scalar registers) -- count() adds, add_counters() flushes
+                   // kernel that already spills scalar registers) -- count() adds, add_counters() flushes.  Lanes 61-63 are the
+                   // mailbox of the incumbent hooks (post_terminal): the search kernel has no register to give them either.
     u16 *stage;    // this wave's LDS staging run of A actions (kernels that can create nodes), else null
     u64 *vm;       // this wave's LDS scratch for gen_valid_moves ([VM_WORDS]), with `stage`
     u32 *vmask;    // this wave's LDS bit mask over a node's legal moves ([MAX_MASK_WORDS]; kernels that can add visited edges), else null
@@ -569,6 +598,20 @@ template <typename row_t, bool BIG = true> struct Tree {
         va.next = p.va_next + (size_t)g * p.n_vchunks; va.stack = p.va_stack + (size_t)g * p.n_vchunks; va.tf = p.va_tf + (size_t)g * 2;
     }
     __device__ __forceinline__ void count(int k, u32 v = 1u) { cnt += lane_id() == k ? v : 0u; }
+    // A terminal node that materialize has just created, with its score r: id + 1 in lane 63 of cnt (0: none), the halves of r in lanes
+    // 61 and 62.  Whoever arrives at the node takes it (take_terminal) and offers it as the episode's incumbent.
+    __device__ __forceinline__ void post_terminal(u32 id, double r) {
+        const u64 b = (u64)__double_as_longlong(r);
+        const int l = lane_id();
+        cnt = l == 63 ? id + 1u : l == 62 ? (u32)(b >> 32) : l == 61 ? (u32)b : cnt;
+    }
+    __device__ __forceinline__ bool terminal_posted() const { return __builtin_amdgcn_readlane((int)cnt, 63) != 0; }
+    __device__ __forceinline__ u32 take_terminal(double *r) {
+        const u32 id = (u32)__builtin_amdgcn_readlane((int)cnt, 63) - 1u;
+        *r = __longlong_as_double((long long)(((u64)(u32)__builtin_amdgcn_readlane((int)cnt, 62) << 32) | (u64)(u32)__builtin_amdgcn_readlane((int)cnt, 61)));
+        if (lane_id() >= 61) cnt = 0;
+        return id;
+    }
     // one coalesced read-modify-write of the slot's sixteen 64-bit totals (plain stores: the slot's own wave is their only writer)
     __device__ void flush_counters() {
         const int lane = lane_id();
@@ -693,7 +736,8 @@ template <typename row_t, bool BIG = true> struct Tree {
     // A state seen for the first time: the Es / Vs part of MCTS.search (MCTS_bpp.py:78-79 getGameEnded ->
     // has_valid_moves / getRankedReward; :88 getValidMoves).  Allocates the node, stores its key, its legal
     // moves as a run of actions (their priors are filled in by the commit kernel after the evaluator ran) or its
-    // terminal value.  Returns the node id or NONE32 on arena overflow.
+    // terminal value.  Returns the node id or NONE32 on arena overflow.  A new terminal node is posted with its score r (getRankedReward,
+    // BinPackingGame.py:188-212) for the incumbent hooks (post_terminal).
     __device__ u32 materialize(row_t myrow, u64 rem0, u64 rem1, u64 h, u32 insert_slot) {
         if (n_nodes >= (u32)p.node_cap || insert_slot == NONE32) {
             if (lane_id() == 0) set_error(p, ERR_NODE_CAP);
@@ -728,6 +772,7 @@ template <typename row_t, bool BIG = true> struct Tree {
             int e = ranked_reward<row_t>(myrow, p.H, p.W, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r);
             if (e == 2) { e = tie_value<row_t>(myrow, p.H, p.N, rem0, rem1, p.tie_salt); hd.flags = (u8)(RP_KIND_F64 << 2); }
             hd.term = (int8_t)e;
+            post_terminal(id, r);
         }
         if (lane_id() == 0) {
             hdr[id] = hd;
@@ -979,6 +1024,52 @@ struct EpisodeEnd {
     u64 filled;
 };
 
+// Incumbent of slot g's episode (rp_set_incumbent): the terminal state with the largest score r among those MATERIALISED in the slot's
+// tree during the episode, the first created among equals.  A terminal is scored when its node is created (MCTS_bpp.py:78-83 fills Es
+// once per state; getRankedReward, BinPackingGame.py:188-212), so node creation is the only event that can change the incumbent:
+// materialize posts (node, r) in the wave's registers (Tree::post_terminal) and the code that called it takes the terminal from there.
+// The move routine, a terminal initial state and rp_begin_episodes offer it on the spot.  k_search has neither vector nor scalar
+// registers to spare (it spills both), so it looks once per simulation whether a terminal was posted; if so, and incumbents are on, it
+// stores (node, r) in DP::inc_new and its path where a leaf's path goes and ends the slot's launch, and k_incumbent, launched behind
+// it, makes the offer from there.  The actions are the `prefix` moves played so far, the `depth` edges of the creating simulation's
+// path (lane l holds visited entry pe / node pn of level l, lanes of the second pair levels 64 ..) and `extra` (>= 0: one more action,
+// the move being played).
+template <typename row_t, bool BIG>
+__device__ void incumbent_offer(const DP &p, const Tree<row_t, BIG> &t, int g, u32 node, double r, int prefix, int depth, int extra, u32 pe0, u32 pn0, u32 pe1, u32 pn1) {
+    const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
+    const int lane = lane_id();
+    int *meta = rec.meta();
+    const int have = uni(meta[1]), updates = uni(meta[3]) + 1;
+    const bool better = have < 0 || r > *rec.score();  // strictly better only: the first created among equals stays
+    wave_sync();
+    if (!better) return;
+    u16 *action = rec.action();
+    const u16 *played = rec.played();
+    for (int q = lane; q < prefix && q < p.N; q += 64) action[q] = played[q];
+    if (lane < depth && prefix + lane < p.N) action[prefix + lane] = t.pAct[t.hdr[pn0].prior_off + t.vis[pe0].idx];
+    if (BIG && lane + 64 < depth && prefix + lane + 64 < p.N) action[prefix + lane + 64] = t.pAct[t.hdr[pn1].prior_off + t.vis[pe1].idx];
+    int moves = prefix + depth;
+    if (extra >= 0) {
+        if (lane == 0 && moves < p.N) action[moves] = (u16)extra;
+        moves++;
+    }
+    if (lane < p.H) rec.board()[lane] = (u64)((const row_t *)(t.key + (size_t)node * p.KW))[lane];
+    if (lane == 0) {
+        *rec.score() = r;
+        meta[0] = (int)t.hdr[node].term; meta[1] = moves; meta[2] = prefix; meta[3] = updates;
+    }
+    wave_sync();
+}
+// an episode starts without an incumbent (restart_slot_impl, k_set_roots with clear_tree)
+__device__ __forceinline__ void incumbent_reset(const DP &p, int g) {
+    if (p.inc && lane_id() == 0) {
+        const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
+        *rec.score() = 0.0; p.inc_new[g].node = NONE32;
+        int *m = rec.meta();
+        m[0] = 0; m[1] = -1; m[2] = 0; m[3] = 0;
+    }
+}
+
 // The finished record of slot g's episode: the score, the examples' values, the ring entry and -- under the trace -- the episode's moves
 // and final bin at the ring index of its record.  The last move comes from `e`, the earlier ones from the slot's running trace;
 // moves == 0 leaves a record without moves whose final bin is the initial state.  Leaves phase EPISODE_DONE.  The one copy of this code
@@ -1011,8 +1102,16 @@ __device__ void finish_episode_impl(const DP &p, Tree<row_t, BIG> &t, int g, con
             set_error(p, ERR_FINISHED_CAP);
         }
     }
+    if (p.tr_action || p.inc) idx = __shfl(idx, 0);
+    if (p.inc && idx < p.fin_cap) {  // the episode's incumbent, at the ring index of its record (its own final state was offered)
+        const IncRec src(p.inc + (size_t)g * p.inc_stride, p.H, p.N), dst(p.fin_inc + (size_t)idx * p.inc_stride, p.H, p.N);
+        const int inc_moves = src.meta()[1];
+        for (int q = lane; q < p.N; q += 64) dst.action()[q] = q < inc_moves ? src.action()[q] : (u16)0;
+        if (lane < p.H) dst.board()[lane] = src.board()[lane];
+        if (lane < 4) dst.meta()[lane] = src.meta()[lane];
+        if (lane == 0) *dst.score() = *src.score();
+    }
     if (p.tr_action) {  // the episode's trace and final bin, at the ring index of its record
-        idx = __shfl(idx, 0);
         if (idx < p.fin_cap) {
             for (int q = lane; q < p.N; q += 64) {  // earlier moves were stored by earlier launches (a launch plays one move per slot)
                 const bool earlier = q < moves - 1, last = q == moves - 1;
@@ -1121,6 +1220,15 @@ __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u3
         child = t.resolve_child(root, chosen, chosen_action, &was_new);
         wave_sync();
         if (child == NONE32) { if (lane == 0) p.phase[g] = RP_PHASE_FAILED; return none; }
+        if (t.terminal_posted()) {  // a move the search never tried ended on a terminal nobody had seen: a path of one move
+            double r;
+            const u32 nt = t.take_terminal(&r);
+            if (p.inc) incumbent_offer(p, t, g, nt, r, uni(p.moves[g]), 0, chosen_action, NONE32, NONE32, NONE32, NONE32);
+        }
+    }
+    if (p.inc) {  // the played actions are the prefix of every later incumbent of this episode
+        const int mv = p.moves[g];
+        if (lane == 0 && mv < p.N) IncRec(p.inc + (size_t)g * p.inc_stride, p.H, p.N).played()[mv] = (u16)chosen_action;
     }
     if (p.max_examples > 0) {  // trainExamples.append([state, pi, None]) (CoachBPP.py:80)
         unsigned long long idx = 0, sp = 0;
@@ -1207,6 +1315,7 @@ __device__ EpisodeEnd restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g,
         p.bl[g] = pd.bl ? pd.bl[idx] : *p.g_bl; p.has_buf[g] = pd.has_buf ? (int)pd.has_buf[idx] : *p.g_has_buf;
         p.last_outcome[g] = 0; p.last_score[g] = 0.0;
     }
+    incumbent_reset(p, g);
     t.n_nodes = 0;
     t.reset_arenas();
     wave_sync();
@@ -1222,7 +1331,13 @@ __device__ EpisodeEnd restart_slot_impl(const DP &p, Tree<row_t, BIG> &t, int g,
     wave_sync();
     if (lane == 0) { p.root[g] = root; p.phase[g] = root == NONE32 ? RP_PHASE_FAILED : RP_PHASE_RUNNING; }
     if (root == NONE32) return none;
-    return EpisodeEnd{uni((int)t.hdr[root].term), 0, 0, root, 0ull};  // getGameEnded(initial state) != 0: nothing to search
+    const int term = uni((int)t.hdr[root].term);
+    if (t.terminal_posted()) {  // a terminal initial state is its episode's incumbent: no moves
+        double r;
+        const u32 nt = t.take_terminal(&r);
+        if (p.inc) incumbent_offer(p, t, g, nt, r, 0, 0, -1, NONE32, NONE32, NONE32, NONE32);
+    }
+    return EpisodeEnd{term, 0, 0, root, 0ull};  // getGameEnded(initial state) != 0: nothing to search
 }
 
 // Writes the record of an episode that has ended and, under auto_restart, gives the slot the next instance of the pool -- again while
@@ -1267,7 +1382,20 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, SEARCH_WAVES) k_search(D
     phase = uni(phase); root = uni(root); sims_done = uni(sims_done); t.n_nodes = uni(t.n_nodes);
     if (phase != RP_PHASE_RUNNING) return;  // MOVE_READY slots were handled by k_moves just before this launch
     const bool key_ahead = t.packed();  // a node's key can ride along with its header (one load instruction)
-    int launched = 0;
+    int launched = 0, depth = 0;
+    u32 pe0 = NONE32, pn0 = NONE32, pe1 = NONE32, pn1 = NONE32;  // the simulation's path: lane l holds level l (second pair: level 64 + l)
+    // A new terminal and the path that created it, for k_incumbent.  Where this is done is a matter of registers alone (the kernel spills
+    // both kinds): behind the loop the 32-bit-row kernels need fewer of them than the parent commit's, the 64-bit-row kernels more, and
+    // at the loop's foot it is the other way round (make resource-usage).
+    constexpr bool HAND_OVER_LATE = sizeof(row_t) == 4;
+    auto hand_over = [&]() {
+        double r;
+        const u32 nt = t.take_terminal(&r);
+        u32 *pe = p.path_edge + (size_t)g * p.N, *pn = p.path_node + (size_t)g * p.N;
+        if (lane < depth) { pe[lane] = pe0; pn[lane] = pn0; }
+        if (BIG && lane + 64 < depth) { pe[lane + 64] = pe1; pn[lane + 64] = pn1; }
+        if (lane == 0) { p.path_len[g] = depth; p.inc_new[g].r = r; p.inc_new[g].node = nt; }
+    };
     for (;;) {
         // A slot near the end of its game runs many evaluator-free simulations (terminal hits); the cap bounds the
         // launch's tail so one such slot cannot stall the whole wave.  Pure scheduling: results do not depend on it.
@@ -1277,8 +1405,9 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, SEARCH_WAVES) k_search(D
             break;
         }
         // ---- one simulation ----
-        u32 node = root, pe0 = NONE32, pn0 = NONE32, pe1 = NONE32, pn1 = NONE32;
-        int depth = 0;
+        u32 node = root;
+        pe0 = NONE32; pn0 = NONE32; pe1 = NONE32; pn1 = NONE32;
+        depth = 0;
         double v = 0.0;
         u32 vkind = RP_KIND_WEAK;
         bool need_eval = false, failed = false;
@@ -1335,10 +1464,36 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, SEARCH_WAVES) k_search(D
         launched++;
         t.count(CNT_SIMS);
         wave_sync();
+        // This simulation brought a terminal into the tree: the one moment it can become the episode's incumbent.  The slot's launch ends
+        // here (it goes on in the next one, as under the step cap: scheduling only) and k_incumbent takes it from what hand_over stores.
+        if (t.terminal_posted() && p.inc_new) {
+            if (!HAND_OVER_LATE) hand_over();
+            break;
+        }
     }
+    if (HAND_OVER_LATE && t.terminal_posted() && p.inc_new) hand_over();
     t.store_sizes();
     if (lane == 0) { p.phase[g] = phase; p.sims_done[g] = sims_done; }
     t.flush_counters();
+}
+
+// The incumbent offer of a terminal that k_search created (incumbent_offer): launched right behind k_search while incumbents are on.  The
+// path k_search stored is still the slot's latest, and nothing it refers to has been recycled: moves are played by later launches.
+template <typename row_t>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_incumbent(DP p) {
+    const int g = blockIdx.x * WAVES_PER_BLOCK + wave_in_block(), lane = lane_id();
+    if (g >= p.G || !p.inc_new) return;
+    const u32 node = uni(p.inc_new[g].node);
+    if (node == NONE32) return;
+    Tree<row_t> t(p, g);
+    int depth = uni(p.path_len[g]);
+    if (depth < 0 || depth > p.N) depth = 0;
+    const u32 *pe = p.path_edge + (size_t)g * p.N, *pn = p.path_node + (size_t)g * p.N;
+    u32 pe0 = NONE32, pn0 = NONE32, pe1 = NONE32, pn1 = NONE32;
+    if (lane < depth) { pe0 = pe[lane]; pn0 = pn[lane]; }
+    if (lane + 64 < depth) { pe1 = pe[lane + 64]; pn1 = pn[lane + 64]; }
+    incumbent_offer(p, t, g, node, p.inc_new[g].r, uni(p.moves[g]), depth, -1, pe0, pn0, pe1, pn1);
+    if (lane == 0) p.inc_new[g].node = NONE32;
 }
 
 // CoachBPP.executeEpisode's move for every slot whose search budget is spent (RP_MOVE_ARGMAX_FIRST / RP_MOVE_SAMPLE), and the
@@ -1983,6 +2138,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_set_roots(DP p, int fi
             p.bl[g] = *p.g_bl; p.has_buf[g] = *p.g_has_buf;  // rewards_list snapshot for this episode
             p.last_outcome[g] = 0; p.last_score[g] = 0.0;
         }
+        incumbent_reset(p, g);
         wave_sync();
     }
     extern __shared__ u16 s_stage[];
@@ -1997,6 +2153,12 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_set_roots(DP p, int fi
     }
     bool was_new;
     u32 id = t.find_or_materialize(myrow, rem0, rem1, &was_new);
+    if (t.terminal_posted()) {  // a new episode whose first state is terminal
+        double r;
+        const u32 nt = t.take_terminal(&r);
+        wave_sync();
+        if (p.inc && clear_tree) incumbent_offer(p, t, g, nt, r, 0, 0, -1, NONE32, NONE32, NONE32, NONE32);
+    }
     t.store_sizes();
     t.flush_counters();
     if (lane == 0) {
@@ -4186,6 +4348,9 @@ struct rp_ctx {
     // placement trace buffers (rp_set_trace): allocated on the first enable, kept until destroy; the DP holds them only while it is on
     u16 *tr_action = nullptr, *fin_tr_action = nullptr;
     u64 *tr_rows = nullptr, *fin_tr_rows = nullptr, *fin_board = nullptr;
+    // incumbent records (rp_set_incumbent): the same life cycle
+    u8 *inc = nullptr, *fin_inc = nullptr;
+    IncNew *inc_new = nullptr;
 };
 
 static std::string g_create_error;
@@ -4979,6 +5144,8 @@ extern "C" int rp_begin_episodes(rp_ctx *ctx, int32_t first, int32_t count, cons
 
 extern "C" int rp_set_roots(rp_ctx *ctx, int32_t first, int32_t count, const uint64_t *rows, const uint8_t *remaining) {
     if (!ctx || first < 0 || count < 0 || first + count > ctx->d.G || !rows || !remaining) return fail(ctx, RP_ERR_ARG, "rp_set_roots: bad argument");
+    if (ctx->d.inc)
+        return fail(ctx, RP_ERR_STATE, "rp_set_roots: incumbents are on (rp_set_incumbent) and the moves that lead to the new root are not known to the engine");
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);
@@ -5052,6 +5219,79 @@ extern "C" int rp_set_trace(rp_ctx *ctx, int32_t enable) {
     return RP_OK;
 }
 
+// the incumbent outputs of rp_pop_finished_best and rp_incumbents; every member may be NULL
+struct BestOut {
+    double *score = nullptr;
+    int32_t *outcome = nullptr, *moves = nullptr, *prefix = nullptr, *updates = nullptr;
+    uint16_t *action = nullptr;
+    uint64_t *board = nullptr;
+    bool any() const { return score || outcome || moves || prefix || updates || action || board; }
+};
+// n incumbent records in host memory -> the caller's arrays; a record without an incumbent: moves = -1, zeros elsewhere
+static void unpack_incumbents(const DP &d, u8 *buf, size_t n, const BestOut &out) {
+    for (size_t k = 0; k < n; ++k) {
+        const IncRec rec(buf + k * d.inc_stride, d.H, d.N);
+        const int *m = rec.meta();
+        const int moves = m[1];
+        const bool have = moves >= 0;
+        if (out.score) out.score[k] = have ? *rec.score() : 0.0;
+        if (out.outcome) out.outcome[k] = have ? m[0] : 0;
+        if (out.moves) out.moves[k] = have ? moves : -1;
+        if (out.prefix) out.prefix[k] = have ? m[2] : 0;
+        if (out.updates) out.updates[k] = have ? m[3] : 0;
+        if (out.action) for (int q = 0; q < d.N; ++q) out.action[k * d.N + q] = q < moves ? rec.action()[q] : (u16)0;
+        if (out.board) for (int r = 0; r < d.H; ++r) out.board[k * d.H + r] = have ? rec.board()[r] : 0ull;
+    }
+}
+
+extern "C" int rp_set_incumbent(rp_ctx *ctx, int32_t enable) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_incumbent: bad argument");
+    DP &d = ctx->d;
+    {   // not while episodes are being played: the terminals their trees already hold would be missing
+        std::vector<int> ph((size_t)d.G);
+        HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int g = 0; g < d.G; ++g)
+            if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY)
+                return fail(ctx, RP_ERR_STATE, "rp_set_incumbent: slot %d is in the middle of an episode; switch incumbents between pools", g);
+    }
+    if (enable && !ctx->inc) {  // the three buffers or none, as rp_set_trace: (G + fin_cap) * stride + 16 G bytes
+        const size_t stride = IncRec::stride(d.H, d.N);
+        u8 *run = nullptr, *fin = nullptr;
+        IncNew *nw = nullptr;
+        ALLOC(ctx, run, (size_t)d.G * stride); ALLOC(ctx, fin, (size_t)d.fin_cap * stride); ALLOC(ctx, nw, (size_t)d.G);
+        // no slot has an incumbent (moves = -1) or a terminal on its way to k_incumbent (node = NONE32) before its first episode begins
+        std::vector<u8> none((size_t)d.G * stride, 0);
+        for (int g = 0; g < d.G; ++g) IncRec(none.data() + (size_t)g * stride, d.H, d.N).meta()[1] = -1;
+        HIPCHK(ctx, hipMemcpyAsync(run, none.data(), none.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(nw, 0xFF, (size_t)d.G * sizeof(IncNew), ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->inc = run; ctx->fin_inc = fin; ctx->inc_new = nw;
+    }
+    d.inc = enable ? ctx->inc : nullptr;
+    d.fin_inc = enable ? ctx->fin_inc : nullptr;
+    d.inc_new = enable ? ctx->inc_new : nullptr;
+    d.inc_stride = (int)IncRec::stride(d.H, d.N);
+    return RP_OK;
+}
+
+// Running incumbents of slots first .. first + count - 1: host copies; moves = -1 (and zeros elsewhere) where the episode has none yet.
+extern "C" int rp_incumbents(rp_ctx *ctx, int32_t first, int32_t count, double *score_out, int32_t *outcome_out, int32_t *moves_out, int32_t *prefix_out,
+                             int32_t *updates_out, uint16_t *action_out, uint64_t *board_out) {
+    if (!ctx || first < 0 || count < 0 || first + count > ctx->d.G) return fail(ctx, RP_ERR_ARG, "rp_incumbents: bad argument");
+    const DP &d = ctx->d;
+    if (!d.inc) return fail(ctx, RP_ERR_ARG, "rp_incumbents: incumbents are off (rp_set_incumbent(ctx, 1) before the episodes begin)");
+    if (count == 0) return RP_OK;
+    std::vector<u8> buf((size_t)count * d.inc_stride);
+    HIPCHK(ctx, hipMemcpyAsync(buf.data(), d.inc + (size_t)first * d.inc_stride, buf.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    BestOut out;
+    out.score = score_out; out.outcome = outcome_out; out.moves = moves_out; out.prefix = prefix_out; out.updates = updates_out;
+    out.action = action_out; out.board = board_out;
+    unpack_incumbents(d, buf.data(), (size_t)count, out);
+    return check_device_error(ctx);
+}
+
 extern "C" int rp_set_sims(rp_ctx *ctx, int32_t sims) {
     if (!ctx || sims < 0 || (int64_t)sims * (ctx->d.N + 1) >= (int64_t)NSA_MASK) return fail(ctx, RP_ERR_ARG, "rp_set_sims: bad argument");
     ctx->d.sims = sims;  // the device view is passed by value at every launch
@@ -5072,6 +5312,7 @@ extern "C" int rp_search_step(rp_ctx *ctx, int32_t *n_leaves_out) {
     DP &d = ctx->d;
     int rc = d.move_rule != RP_MOVE_EXTERNAL ? launch_staged(ctx, "k_moves", GEO_KERNEL(ctx, false, k_moves<row_t>), d.G, d) : RP_OK;
     if (rc == RP_OK) rc = launch_staged(ctx, "k_search", GEO_KERNEL(ctx, d.N > 64, k_search<row_t, geo.flag>), d.G, d);
+    if (rc == RP_OK && d.inc) rc = launch_waves(ctx, "k_incumbent", GEO_KERNEL(ctx, false, k_incumbent<row_t>), d.G, d);
     if (rc != RP_OK) return rc;
     // Without a count request nothing is synchronised and evaluator row b belongs to slot b (fixed shapes for graph capture);
     // with one, the waiting slots are listed in slot order and rows follow that list.
@@ -5376,7 +5617,7 @@ extern "C" int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const
 }
 
 static int pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out, int32_t *moves_out,
-                        uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, int64_t *n_out) {
+                        uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, int64_t *n_out, const BestOut &best = BestOut()) {
     const DP &d = ctx->d;
     int cnt = 0;
     HIPCHK(ctx, hipMemcpyAsync(&cnt, d.fin_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -5393,7 +5634,13 @@ static int pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, in
     if (action_out) HIPCHK(ctx, hipMemcpyAsync(action_out, d.fin_tr_action + off * d.N, n * d.N * sizeof(u16), hipMemcpyDeviceToHost, ctx->stream));
     if (rows_out) HIPCHK(ctx, hipMemcpyAsync(rows_out, d.fin_tr_rows + off * d.N, n * d.N * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     if (board_out) HIPCHK(ctx, hipMemcpyAsync(board_out, d.fin_board + off * d.H, n * d.H * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<u8> inc;
+    if (best.any()) {
+        inc.resize((size_t)n * d.inc_stride);
+        HIPCHK(ctx, hipMemcpyAsync(inc.data(), d.fin_inc + off * d.inc_stride, inc.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (best.any()) unpack_incumbents(d, inc.data(), (size_t)n, best);
     ctx->fin_popped += n;
     if (ctx->fin_popped == cnt) {  // ring drained: rewind
         HIPCHK(ctx, hipMemsetAsync(d.fin_count, 0, sizeof(int), ctx->stream));
@@ -5414,6 +5661,20 @@ extern "C" int rp_pop_finished_packings(rp_ctx *ctx, int64_t max_n, uint64_t *ep
     if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_packings: bad argument");
     if (!ctx->d.tr_action) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_packings: the placement trace is off (rp_set_trace(ctx, 1) before the pool begins)");
     return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out);
+}
+
+extern "C" int rp_pop_finished_best(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out, int32_t *moves_out,
+                                    uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, double *best_score_out, int32_t *best_outcome_out,
+                                    int32_t *best_moves_out, int32_t *best_prefix_out, int32_t *best_updates_out, uint16_t *best_action_out,
+                                    uint64_t *best_board_out, int64_t *n_out) {
+    if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best: bad argument");
+    if (!ctx->d.inc) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best: incumbents are off (rp_set_incumbent(ctx, 1) before the pool begins)");
+    if ((action_out || rows_out || board_out) && !ctx->d.tr_action)
+        return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best: a trace output was requested while the placement trace is off (rp_set_trace)");
+    BestOut best;
+    best.score = best_score_out; best.outcome = best_outcome_out; best.moves = best_moves_out; best.prefix = best_prefix_out;
+    best.updates = best_updates_out; best.action = best_action_out; best.board = best_board_out;
+    return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out, best);
 }
 
 // The pool's three functions.  A setter makes every check that can refuse BEFORE pool_reserve: a refused call leaves the previous pool

@@ -41,6 +41,8 @@ class _Group:
         self.eng.set_compact_rows(owner.compact_rows)
         if owner.record_packings:
             self.eng.set_trace(True)
+        if owner.record_best:
+            self.eng.set_incumbent(True)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         self.wide_logits = owner.wide_logits
@@ -123,7 +125,7 @@ class _Group:
 class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
-                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8):
+                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False):
         """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
         uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
         or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
@@ -132,6 +134,9 @@ class BatchedSelfPlay:
         commit kernel, as on every smaller board); False keeps torch.softmax + rp_commit_eval for them (the A/B switch).
         record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
         return and the finished episodes' layouts are collected for pop_packings().
+        record_best: the engines keep every episode's incumbent (rp_set_incumbent) -- the best complete packing its search tree saw,
+        which the played one cannot beat; the finished episodes' incumbents are collected for pop_best_packings().  Tree terminals only:
+        the playouts of evaluator="rollout" do not feed it.
         host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
         eagerly with one host round trip each.  tie_salt: salt of the deterministic `r == bl` tie (default: derived from seed)."""
@@ -161,7 +166,9 @@ class BatchedSelfPlay:
         self.tie_salt, self.host_evaluator = tie_salt, host_evaluator
         self.wide_logits = bool(wide_logits)
         self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
+        self.record_best = bool(record_best)  # likewise
         self._packings = []
+        self._best = []
         self._pool_items = None
         self._pool_initial = None
         self.use_graph = bool(use_graph) and host_evaluator is None
@@ -258,6 +265,14 @@ class BatchedSelfPlay:
         self._packings = []
         self.invalidate_graph()
 
+    def set_record_best(self, on=True):
+        """Switches the incumbents of every group between pools (refused while episodes are being played); re-captures the waves."""
+        for g in self.groups:
+            g.eng.set_incumbent(on)
+        self.record_best = bool(on)
+        self._best = []
+        self.invalidate_graph()
+
     # ---- whole pools -------------------------------------------------------------------------------
     def _blocks(self, n):
         """Contiguous block of the pool per group: [(lo, hi)]; instance i has episode id first_id + i."""
@@ -318,7 +333,7 @@ class BatchedSelfPlay:
         self.n_instances = n
         self._check_meta(n, episode_ids, thresholds)
         initial = self._check_initial(n, initial_rows, initial_remaining, max_h)
-        self._pool_items = (episode_ids, items) if self.record_packings else None
+        self._pool_items = (episode_ids, items) if self.record_packings or self.record_best else None
         self._pool_initial = initial
         torch.cuda.synchronize(self.device)  # the evaluator's weights may just have been trained on another stream
         if self.host_evaluator is None and self.fuse_elementwise and self.dense_small_convs:
@@ -369,29 +384,54 @@ class BatchedSelfPlay:
 
     def pop_finished(self):
         """(episode ids, outcomes, scores, moves) of the episodes finished since the last call, sorted by id.  With record_packings
-        their layouts are set aside for pop_packings()."""
-        parts = []
+        their layouts are set aside for pop_packings(), with record_best their incumbents for pop_best_packings()."""
+        parts, best = [], []
         for g in self.groups:
-            rec = g.eng.pop_finished(packings=self.record_packings)
+            rec = g.eng.pop_finished(packings=self.record_packings, best=self.record_best)
+            if self.record_best:
+                best.append(rec[-1]); rec = rec[:-1]
             parts.append((rec[0].astype(np.int64),) + tuple(rec[1:]))
         ids = np.concatenate([p[0] for p in parts]); order = np.argsort(ids, kind="stable")
         out = tuple(np.concatenate([p[j] for p in parts])[order] for j in range(len(parts[0])))
         if self.record_packings and len(ids):
             self._keep_packings(*out)
+        if self.record_best and len(ids):
+            self._keep_best(out[0], {k: np.concatenate([b[k] for b in best])[order] for k in best[0]})
         return out[:4]
 
-    def _keep_packings(self, ids, outcome, score, moves, action, rows, board):
-        """Packing records of finished episodes of the current pool (their item sizes come from it)."""
-        from .solve import Packing
+    def _pool_lookup(self):
+        """-> (item sizes [n, N, 2] of the current pool, {episode id: instance index})."""
         if self._pool_items is None:
-            raise RuntimeError("episodes finished before a pool was started with record_packings on")
+            raise RuntimeError("episodes finished before a pool was started with record_packings or record_best on")
         episode_ids, items = self._pool_items
         if isinstance(items, tuple):  # a pool of generator seeds: the same device generator gives the sizes back
             seeds, bin_w, bin_h = items
             items = self.eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
             self._pool_items = (episode_ids, items)
         pool_ids = self.first_id + np.arange(self.n_instances, dtype=np.int64) if episode_ids is None else np.asarray(episode_ids, dtype=np.int64)
-        index = {int(e): k for k, e in enumerate(pool_ids)}
+        return items, {int(e): k for k, e in enumerate(pool_ids)}
+
+    def _keep_best(self, ids, best):
+        """Incumbents of finished episodes of the current pool as Packings.  The device keeps an incumbent's actions and final bin only;
+        the rows every move filled are replayed on the host (solve.replay_rows) and the replay must end on the device's bin."""
+        from .solve import Packing, replay_rows
+        items, index = self._pool_lookup()
+        initial = self._pool_initial
+        for k in range(len(ids)):
+            m, i = int(best["moves"][k]), index[int(ids[k])]
+            start = {} if initial is None else dict(initial_board=initial[0][i], present=initial[1][i] != 0)
+            actions = best["action"][k, :m].astype(np.int32)
+            rows, board = replay_rows(self.W, self.H, items[i], actions, start.get("initial_board"))
+            if not np.array_equal(board, best["board"][k]):
+                raise RuntimeError("episode %d: the incumbent's actions replay to another bin than the engine recorded" % int(ids[k]))
+            p = Packing(int(ids[k]), self.W, items[i], actions, rows, board, int(best["outcome"][k]), float(best["score"][k]), **start)
+            p.prefix, p.updates = int(best["prefix"][k]), int(best["updates"][k])
+            self._best.append(p)
+
+    def _keep_packings(self, ids, outcome, score, moves, action, rows, board):
+        """Packing records of finished episodes of the current pool (their item sizes come from it)."""
+        from .solve import Packing
+        items, index = self._pool_lookup()
         initial = self._pool_initial
         for k in range(len(ids)):
             m, i = int(moves[k]), index[int(ids[k])]
@@ -402,6 +442,13 @@ class BatchedSelfPlay:
         """solve.Packing of every episode that finished (and was popped: run() does) since the last call, sorted by episode id."""
         out = sorted(self._packings, key=lambda p: p.episode_id)
         self._packings = []
+        return out
+
+    def pop_best_packings(self):
+        """The incumbent of every episode that finished (and was popped: run() does) since the last call as a solve.Packing with
+        `prefix` and `updates` set, sorted by episode id (record_best)."""
+        out = sorted(self._best, key=lambda p: p.episode_id)
+        self._best = []
         return out
 
     def arena_peak(self):

@@ -27,7 +27,13 @@ class Packing:
     Plain data: episode_id, W, item_wh uint8 [N, 2] (w, h), actions int32 [moves], rows uint64 [moves] (bit r = bin row r),
     board uint64 [H] (bit c of board[r] = cell (r, c)), outcome (+-1, the ranked result), score; and where the episode started
     (rp_set_instance_initial): initial_board uint64 [H], the cells set before the first move (default: none), and present bool [N],
-    the items that took part (default: all)."""
+    the items that took part (default: all).
+
+    An incumbent (pack(..., best=True), BatchedSelfPlay.pop_best_packings) is a Packing too: the best complete packing the episode's search
+    tree saw.  It also carries prefix (how many of its moves had been played when the search found it), updates (how often the episode's
+    incumbent was replaced, the first entry included) and played (the Packing the move rule played, where it was recorded); all three
+    are None on a played Packing."""
+    prefix = updates = played = None
 
     def __init__(self, episode_id, W, item_wh, actions, rows, board, outcome=0, score=0.0, initial_board=None, present=None):
         self.episode_id = int(episode_id)
@@ -163,6 +169,37 @@ class Packing:
     __hash__ = None
 
 
+def replay_rows(W, H, item_wh, actions, initial_board=None):
+    """Bin.execute_move (BinPackingLogic.py:95-109) over a sequence of actions, on the host -> (rows uint64 [moves], board uint64 [H]):
+    rows[m] = mask of the bin rows move m filled, board = the bin after the last move.  action = item * W + column; the item's cells
+    [column, column + w) -- clipped at W like the NumPy slice -- go to the first h rows, scanning from row 0, in which they are all
+    free; fewer than h where the bin runs out.  The engine stores an incumbent as its actions and final bin only; this gives the
+    per-move rows back.  initial_board: uint64 [H] row masks (default: the empty bin)."""
+    W, H = int(W), int(H)
+    item_wh = np.asarray(item_wh).reshape(-1, 2)
+    board = [0] * H if initial_board is None else [int(x) for x in np.asarray(initial_board, dtype=np.uint64).reshape(-1)]
+    if len(board) != H:
+        raise ValueError("initial_board must have one row mask per bin row")
+    full = (1 << W) - 1
+    rows = []
+    for a in np.asarray(actions, dtype=np.int64).reshape(-1):
+        i, j = divmod(int(a), W)
+        if not 0 <= i < len(item_wh):
+            raise ValueError("action %d outside the %d x %d action space" % (a, len(item_wh), W))
+        w, h = int(item_wh[i, 0]), int(item_wh[i, 1])
+        span = (((1 << w) - 1) << j) & full
+        filled = 0
+        for r in range(H):
+            if h == 0:
+                break
+            if board[r] & span == 0:
+                board[r] |= span
+                filled |= 1 << r
+                h -= 1
+        rows.append(filled)
+    return np.array(rows, dtype=np.uint64), np.array(board, dtype=np.uint64)
+
+
 def greedy_rule(args):
     """The engine move rule of greedy play (greedy_a == 0, MCTS_bpp.py:43-49) under args.greedy_tie_break."""
     tie = _opt(args, "greedy_tie_break", "lowest")
@@ -224,18 +261,22 @@ def _check_instances(item_wh, seeds, initial_board, remaining):
 
 
 def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin_w=None, rewards_list=(), first_id=0, initial_board=None,
-                  remaining=None):
+                  remaining=None, best=False):
     """Plays the instances through the driver `sp` (record_packings on) -> list[Packing] in instance order.  The driver's finished
     ring holds four records per slot, so larger pools are played in runs of two per slot.  initial_board / remaining / ragged item_wh:
-    see pack()."""
+    see pack().  best: return every instance's incumbent instead (the driver needs record_best too), its `played` the played Packing."""
     _check_instances(item_wh, seeds, initial_board, remaining)
     if not sp.record_packings:
         raise RuntimeError("the driver was built without record_packings")
+    if best and not sp.record_best:
+        raise RuntimeError("the driver was built without record_best")
     n = len(item_wh) if seeds is None else len(seeds)
     rows0 = rem0 = None
     if seeds is None:
         item_wh, rows0, rem0, own_area = initial_state(sp.W, sp.H, sp.N, item_wh, initial_board, remaining)
     sp.pop_packings()
+    if best:
+        sp.pop_best_packings()
     out = []
     run = max(1, 2 * min(g.G for g in sp.groups) * len(sp.groups))
     for lo in range(0, n, run):
@@ -250,12 +291,19 @@ def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin
         got = sp.pop_packings()
         if [p.episode_id for p in got] != list(range(first_id + lo, first_id + hi)):
             raise RuntimeError("instances %d..%d: %d packings came back" % (lo, hi - 1, len(got)))
+        if best:
+            inc = sp.pop_best_packings()
+            if [p.episode_id for p in inc] != [p.episode_id for p in got]:
+                raise RuntimeError("instances %d..%d: %d incumbents came back" % (lo, hi - 1, len(inc)))
+            for p, played in zip(inc, got):
+                p.played = played
+            got = inc
         out += got
     return out
 
 
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
-         driver=None, seed=0, initial_board=None, remaining=None, **driver_kw):
+         driver=None, seed=0, initial_board=None, remaining=None, best=False, **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
@@ -274,7 +322,11 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     with **driver_kw, records no training examples (max_examples=0) and is closed afterwards.
     Network-free: pack(game, None, args, evaluator="rollout", playouts=K, rewards_list=...) searches with uniform priors and the mean
     outcome of K random playouts per leaf (BatchedSelfPlay's evaluator="rollout").  The playouts are ranked against rewards_list too: with
-    an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one."""
+    an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one.
+    best: return every instance's incumbent instead of the packing that was played: the best complete packing the episode's search tree
+    saw (rp_set_incumbent; the first found among equals), with `prefix`, `updates` and `played` -- the played Packing -- set.  Its own
+    final state is in every episode's tree, so best.score >= best.played.score always.  Tree terminals only: the playouts of
+    evaluator="rollout" are not candidates.  A driver passed in must have been built with record_best=True."""
     from .selfplay import BatchedSelfPlay
     _check_instances(item_wh, seeds, initial_board, remaining)
     n = len(item_wh) if seeds is None else len(seeds)
@@ -283,12 +335,13 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     if sp is None:
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
-        sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, **driver_kw)
+        sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
+                             **driver_kw)
     elif sp.move_rule != rule:
         sp.set_move_rule(rule)
     try:
         return play_packings(sp, item_wh=item_wh, seeds=seeds, total_area=total_area, bin_h=bin_h, bin_w=bin_w, rewards_list=rewards_list,
-                             initial_board=initial_board, remaining=remaining)
+                             initial_board=initial_board, remaining=remaining, best=best)
     finally:
         if driver is None:
             sp.close()
