@@ -39,7 +39,8 @@ extern "C" {
                              7: the commit kernel's softmax as a self-test (rp_selftest_softmax)
                              8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states)
                              9: initial states of pool instances (rp_set_instance_initial)
-                             10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents) */
+                             10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents); additive, same number: playout
+                                 incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -205,7 +206,8 @@ int rp_set_trace(rp_ctx *ctx, int32_t enable);
  * followed by the creating simulation's path, prefix (the number of played moves when it was found), board (the terminal's H row masks)
  * and updates (how often the incumbent was replaced in this episode, the first entry included).  Every finished episode has one -- its
  * own final state was materialised -- so best score >= played score always.  The record is a function of the search alone: not of
- * rp_set_step_cap, rp_set_compact_rows, the slot, or graph replay.  Playouts of rp_rollout_eval do NOT feed it: tree terminals only.
+ * rp_set_step_cap, rp_set_compact_rows, the slot, or graph replay.  Playouts of rp_rollout_eval feed it only under
+ * rp_set_incumbent_playouts (below); by default: tree terminals only.
  * Refused with RP_ERR_STATE while any slot is in the middle of an episode.  The buffers are allocated on the first enable:
  * (G + fin_cap) * S + 16 G bytes, S = 24 + 8 H + 4 N rounded up to a multiple of 8 and fin_cap = max(4 G, 1024) -- 52 MB at 32 768 slots
  * of 20x20 / 32 items in two contexts; with incumbents off nothing is allocated and every hook is one uniform branch.  While they are
@@ -214,6 +216,25 @@ int rp_set_trace(rp_ctx *ctx, int32_t enable);
  * after switching.  Records of episodes that finished while incumbents were off carry none: drain the ring before switching.
  * rp_set_roots is refused while they are on. */
 int rp_set_incumbent(rp_ctx *ctx, int32_t enable);
+/* Playout incumbents: with enable != 0 every playout that rp_rollout_eval runs for a waiting leaf (MCTS_bpp.py:87) is a candidate for
+ * the slot's incumbent too -- plain single-player MCTS practice: keep the best rollout.  Off by default; off, records, device bytes and
+ * the playout kernel's path are what they are without this call.  The candidates of an episode form ONE sequence in simulation order.
+ * Tree terminals enter it exactly as under rp_set_incumbent (a slot's launch ends at the simulation that materialised a terminal and
+ * the offer is made behind it).  Each evaluated leaf enters it with one offer, at the place of the simulation that reached it: the
+ * leaf's best playout -- the largest score r (getRankedReward, BinPackingGame.py:188-212, of the playout's final bin), the lowest
+ * playout index j among equals.  An offer replaces the incumbent iff the slot has none yet or r is strictly greater, so `updates`
+ * grows by at most one per leaf, and a second rp_rollout_eval for the same waiting leaves changes nothing.  The record of a playout
+ * incumbent: score = r; outcome = the playout's resolved outcome (the r == bl tie drawn from its final state as for Es); board = the
+ * playout's final rows; prefix = the number of moves played when it was found; action = the played moves, then the leaf's path (the
+ * path rp_search_step stores for the commit), then the playout's own moves, each item * W + column as getNextState takes it
+ * (BinPackingGame.py:58-76); moves = their total.  Two more fields say where a record came from: tree_moves = prefix + path length
+ * (the leaf is reached after that many actions) and playout = j, or -1 for a tree terminal, for which tree_moves == moves.  The record
+ * stays a function of the search alone: not of rp_set_step_cap, rp_set_compact_rows, the slot, graph replay or the evaluator row.  The
+ * episode's own final state is still materialised in the tree, so best score >= played score still holds.
+ * RP_ERR_STATE while incumbents are off and while any slot is in the middle of an episode; rp_set_incumbent(ctx, 0) turns this off too.
+ * The two fields live in a side array of 8 (G + fin_cap) bytes allocated on the first enable; the records' stride S does not change.
+ * Kernel arguments are baked into captured graphs: re-capture after switching. */
+int rp_set_incumbent_playouts(rp_ctx *ctx, int32_t enable);
 /* Changes args.numMCTSSims for the following searches (MCTS_bpp.py:37); rp_search_step stops a slot after this many
  * simulations from its current root. */
 int rp_set_sims(rp_ctx *ctx, int32_t sims);
@@ -329,6 +350,13 @@ int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_
                       const int32_t *total_area, const int32_t *max_h, const uint64_t *episode_id /* NULL: 0 */,
                       const double *rewards, int32_t n_rewards, double alpha, int32_t playouts,
                       int32_t *outcome_out /*[B][playouts]*/, double *score_out, int32_t *moves_out, uint64_t *board_out /*[B][playouts][H]*/);
+/* The action lists of the playouts rp_rollout_states plays (MCTS_bpp.py:87) for the same states, episode ids and seed, through the
+ * recording path of the playout incumbents (rp_set_incumbent_playouts): action_out[b][j][s] = item * W + column of step s of playout j as
+ * getNextState takes it (BinPackingGame.py:58-76), zero for s >= moves_out[b][j].  Replayed from the state they end on the board
+ * rp_rollout_states returns, whose score is BinPackingGame.py:188-212. */
+int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
+                     const uint64_t *episode_id /* NULL: 0 */, int32_t playouts, uint16_t *action_out /*[B][playouts][N]*/,
+                     int32_t *moves_out /*[B][playouts]*/);
 
 /* ---- results ------------------------------------------------------------------------- */
 /* counts[a] = Nsa[(root, a)] (MCTS_bpp.py:40-41), host buffer [count][W*N] */
@@ -366,6 +394,21 @@ int rp_pop_finished_best(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, i
  * may be NULL.  RP_ERR_ARG while incumbents are off. */
 int rp_incumbents(rp_ctx *ctx, int32_t first, int32_t count, double *score_out, int32_t *outcome_out, int32_t *moves_out,
                   int32_t *prefix_out, int32_t *updates_out, uint16_t *action_out /*[count][N]*/, uint64_t *board_out /*[count][H]*/);
+/* rp_pop_finished_best plus where each incumbent came from (rp_set_incumbent_playouts): best_tree_moves_out[k] = the number of actions
+ * after which the search tree was left -- for a playout of MCTS_bpp.py:87 the played moves plus the leaf's path, its own moves
+ * (BinPackingGame.py:58-76) follow in best_action_out[k]; for a tree terminal all of best_moves_out[k] -- and best_playout_out[k] = the
+ * playout's index, -1 for a tree terminal (scores: BinPackingGame.py:188-212).  Same ring and cursor as rp_pop_finished; any output may
+ * be NULL.  RP_ERR_ARG while playout incumbents are off, and for a trace output while the trace is off. */
+int rp_pop_finished_best_playouts(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out,
+                                  int32_t *moves_out, uint16_t *action_out /*[max_n][N]*/, uint64_t *rows_out /*[max_n][N]*/,
+                                  uint64_t *board_out /*[max_n][H]*/, double *best_score_out, int32_t *best_outcome_out,
+                                  int32_t *best_moves_out, int32_t *best_prefix_out, int32_t *best_updates_out,
+                                  uint16_t *best_action_out /*[max_n][N]*/, uint64_t *best_board_out /*[max_n][H]*/,
+                                  int32_t *best_tree_moves_out, int32_t *best_playout_out, int64_t *n_out);
+/* The companion of rp_incumbents: (tree_moves, playout) of the running incumbents of slots first .. first + count - 1 -- a playout of
+ * MCTS_bpp.py:87 (its moves: BinPackingGame.py:58-76, its score: BinPackingGame.py:188-212) or, with playout = -1, a tree terminal;
+ * (0, -1) where the episode has none yet.  Either output may be NULL.  RP_ERR_ARG while playout incumbents are off. */
+int rp_incumbent_sources(rp_ctx *ctx, int32_t first, int32_t count, int32_t *tree_moves_out, int32_t *playout_out);
 /* Engine counters summed over slots since create/reset: [0] simulations, [1] expansions (leaf evaluations),
  * [2] terminal returns, [3] path edges walked, [4] sum of n_valid at selected nodes, [5] sum of n_valid at
  * expanded leaves, [6] transposition links, [7] nodes created, [8] moves played, [9] episodes finished,

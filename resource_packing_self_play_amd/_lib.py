@@ -65,6 +65,8 @@ _SIGS = {
     "rp_set_trace": (C.c_int, [_vp, _i32]),
     "rp_set_incumbent": (C.c_int, [_vp, _i32]),
     "rp_incumbents": (C.c_int, [_vp, _i32, _i32] + [_vp] * 7),
+    "rp_set_incumbent_playouts": (C.c_int, [_vp, _i32]),
+    "rp_incumbent_sources": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_last_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_search_step": (C.c_int, [_vp, _vp]),
     "rp_leaf_planes": (C.c_int, [_vp, _vp, _i64]),
@@ -87,12 +89,14 @@ _SIGS = {
     "rp_commit_eval_host": (C.c_int, [_vp, _vp, _vp, _i32]),
     "rp_rollout_eval": (C.c_int, [_vp, _i32, _vp, _vp, _i64]),
     "rp_rollout_states": (C.c_int, [_vp, _i64] + [_vp] * 7 + [_i32, _f64, _i32] + [_vp] * 4),
+    "rp_rollout_paths": (C.c_int, [_vp, _i64] + [_vp] * 4 + [_i32] + [_vp] * 2),
     "rp_root_counts": (C.c_int, [_vp, _i32, _i32, _vp]),
     "rp_game_status": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rp_advance_roots": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "rp_pop_finished": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "rp_pop_finished_packings": (C.c_int, [_vp, _i64] + [_vp] * 8),
     "rp_pop_finished_best": (C.c_int, [_vp, _i64] + [_vp] * 15),
+    "rp_pop_finished_best_playouts": (C.c_int, [_vp, _i64] + [_vp] * 17),
     "rp_counters": (C.c_int, [_vp, _vp, _i32]),
     "rp_examples_count": (C.c_int, [_vp, _vp]),
     "rp_examples_tensors": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
@@ -185,6 +189,7 @@ class Engine:
         self.pool_size = 0  # size of the pool set last (rp_set_instance_pool*)
         self.trace = False  # placement trace (set_trace)
         self.incumbent = False  # incumbents (set_incumbent)
+        self.incumbent_playouts = False  # playouts are candidates too (set_incumbent_playouts)
 
     def close(self):
         if getattr(self, "h", None):
@@ -320,6 +325,23 @@ class Engine:
         with pop_finished(best=True) and incumbents().  Refused while a slot is in mid-episode; re-capture graphs after switching."""
         self._ck(self.L.rp_set_incumbent(self.h, 1 if on else 0))
         self.incumbent = bool(on)
+        if not on:
+            self.incumbent_playouts = False  # the engine turns the playout mode off with the incumbents
+
+    def set_incumbent_playouts(self, on=True):
+        """Playout incumbents (rp_set_incumbent_playouts): every playout of rollout_eval is a candidate for its slot's incumbent too -- each
+        evaluated leaf offers its best playout (largest score, lowest index among equals).  Needs set_incumbent(True); refused while a slot
+        is in mid-episode; re-capture graphs after switching.  pop_finished(best=True) then also returns tree_moves / playout."""
+        self._ck(self.L.rp_set_incumbent_playouts(self.h, 1 if on else 0))
+        self.incumbent_playouts = bool(on)
+
+    def incumbent_sources(self, first=0, count=None):
+        """Where the running incumbents came from (rp_incumbent_sources) -> dict of tree_moves / playout i32 [n]: the actions after which
+        the tree was left and the playout's index, -1 for a tree terminal; (0, -1) where the episode has none yet."""
+        count = self.G - first if count is None else count
+        d = dict(tree_moves=np.zeros(count, np.int32), playout=np.zeros(count, np.int32))
+        self._ck(self.L.rp_incumbent_sources(self.h, first, count, _ptr(d["tree_moves"]), _ptr(d["playout"])))
+        return d
 
     def incumbents(self, first=0, count=None):
         """Running incumbents of slots first .. first + count - 1 (rp_incumbents) -> dict of score f64 [n], outcome / moves / prefix /
@@ -578,6 +600,18 @@ class Engine:
                                           _ptr(moves), _ptr(board)))
         return outcome, score, moves, board
 
+    def rollout_paths(self, rows, remaining, item_wh, playouts, episode_id=None):
+        """The action lists of the playouts rollout_states plays (rp_rollout_paths) -> (action uint16 [B, K, N], zero past a playout's
+        moves; moves int32 [B, K])."""
+        rows = _arr(rows, np.uint64); B = rows.shape[0]; K = int(playouts)
+        rows = _arr(rows, np.uint64, (B, self.H)); remaining = _arr(remaining, np.uint8, (B, self.N))
+        item_wh = _arr(item_wh, np.uint8, (B, self.N, 2))
+        ids = None if episode_id is None else _arr(episode_id, np.uint64, (B,))
+        Kc = max(K, 0)
+        action = np.zeros((B, Kc, self.N), np.uint16); moves = np.zeros((B, Kc), np.int32)
+        self._ck(self.L.rp_rollout_paths(self.h, B, _ptr(rows), _ptr(remaining), _ptr(item_wh), _ptr(ids), K, _ptr(action), _ptr(moves)))
+        return action, moves
+
     LOGITS_MAX_ACTIONS = 1536  # rp_commit_eval_logits keeps a row in registers, 24 elements per lane
     WIDE_LOGITS_MAX_ACTIONS = 8192  # rp_commit_eval_logits_wide keeps it in LDS: every action space of the ABI
 
@@ -635,7 +669,8 @@ class Engine:
         """(episode ids, outcomes, scores, moves) of up to max_n finished episodes, oldest first; packings=True adds each one's
         placement trace: actions u16 [n, N], filled-row masks u64 [n, N] and final bin rows u64 [n, H] (rp_pop_finished_packings);
         best=True adds, last, a dict with each one's incumbent (rp_pop_finished_best): score f64 [n], outcome / moves / prefix / updates
-        i32 [n], action u16 [n, N] (zero past moves) and board u64 [n, H]."""
+        i32 [n], action u16 [n, N] (zero past moves) and board u64 [n, H] -- and, while playout incumbents are on
+        (set_incumbent_playouts, rp_pop_finished_best_playouts), tree_moves / playout i32 [n]."""
         if max_n is None:  # the ring holds at most max(4 G, 1024) records
             max_n = max(4 * self.G, 1024) if packings or best else 1 << 20
         ids = np.empty(max_n, np.uint64); oc = np.empty(max_n, np.int32); sc = np.empty(max_n, np.float64); mv = np.empty(max_n, np.int32)
@@ -647,8 +682,14 @@ class Engine:
             b = dict(score=np.empty(max_n, np.float64), outcome=np.empty(max_n, np.int32), moves=np.empty(max_n, np.int32),
                      prefix=np.empty(max_n, np.int32), updates=np.empty(max_n, np.int32), action=np.empty((max_n, self.N), np.uint16),
                      board=np.empty((max_n, self.H), np.uint64))
-            self._ck(self.L.rp_pop_finished_best(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), _ptr(act), _ptr(rows), _ptr(board),
-                                                 *[_ptr(b[k]) for k in ("score", "outcome", "moves", "prefix", "updates", "action", "board")], C.byref(n)))
+            fields = ("score", "outcome", "moves", "prefix", "updates", "action", "board")
+            if self.incumbent_playouts:
+                b.update(tree_moves=np.empty(max_n, np.int32), playout=np.empty(max_n, np.int32))
+                self._ck(self.L.rp_pop_finished_best_playouts(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), _ptr(act), _ptr(rows), _ptr(board),
+                                                              *[_ptr(b[k]) for k in fields + ("tree_moves", "playout")], C.byref(n)))
+            else:
+                self._ck(self.L.rp_pop_finished_best(self.h, max_n, _ptr(ids), _ptr(oc), _ptr(sc), _ptr(mv), _ptr(act), _ptr(rows), _ptr(board),
+                                                     *[_ptr(b[k]) for k in fields], C.byref(n)))
             k = n.value
             b = {key: val[:k].copy() for key, val in b.items()}
             if packings:

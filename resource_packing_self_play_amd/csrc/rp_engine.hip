@@ -205,6 +205,9 @@ struct DP {  // device view of a context, passed by value to every kernel
     u8 *fin_inc;   // [fin_cap] finished episodes, at the ring index of their record
     int inc_stride;
     IncNew *inc_new;  // [G] k_search's new terminal, not offered yet
+    // playout incumbents (rp_set_incumbent_playouts): where each record came from, (tree_moves, playout) per slot and, behind them, per
+    // ring entry.  NULL while the mode is off: k_rollout then takes one uniform branch and the tree offers write nothing more.
+    int *inc_src;  // [G + fin_cap][2]
 };
 // the first error of a launch sequence is the one reported (later ones are usually its consequences)
 __device__ __forceinline__ void set_error(const DP &p, int code) { atomicCAS(p.error, 0, code); }
@@ -1033,7 +1036,19 @@ struct EpisodeEnd {
 // stores (node, r) in DP::inc_new and its path where a leaf's path goes and ends the slot's launch, and k_incumbent, launched behind
 // it, makes the offer from there.  The actions are the `prefix` moves played so far, the `depth` edges of the creating simulation's
 // path (lane l holds visited entry pe / node pn of level l, lanes of the second pair levels 64 ..) and `extra` (>= 0: one more action,
-// the move being played).
+// the move being played).  Under rp_set_incumbent_playouts the playouts of k_rollout are candidates of the same sequence (playout_offer),
+// and every offer that enters also notes where it came from in DP::inc_src: a tree terminal (moves, -1).
+// The head of an incumbent's action list, shared by the tree offers and the playout offers (k_rollout): the `prefix` moves played so far,
+// then the `depth` edges of a simulation's path.
+template <typename row_t, bool BIG>
+__device__ __forceinline__ void incumbent_lead(const DP &p, const Tree<row_t, BIG> &t, const IncRec &rec, int prefix, int depth, u32 pe0, u32 pn0, u32 pe1, u32 pn1) {
+    const int lane = lane_id();
+    u16 *action = rec.action();
+    const u16 *played = rec.played();
+    for (int q = lane; q < prefix && q < p.N; q += 64) action[q] = played[q];
+    if (lane < depth && prefix + lane < p.N) action[prefix + lane] = t.pAct[t.hdr[pn0].prior_off + t.vis[pe0].idx];
+    if (BIG && lane + 64 < depth && prefix + lane + 64 < p.N) action[prefix + lane + 64] = t.pAct[t.hdr[pn1].prior_off + t.vis[pe1].idx];
+}
 template <typename row_t, bool BIG>
 __device__ void incumbent_offer(const DP &p, const Tree<row_t, BIG> &t, int g, u32 node, double r, int prefix, int depth, int extra, u32 pe0, u32 pn0, u32 pe1, u32 pn1) {
     const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
@@ -1044,10 +1059,7 @@ __device__ void incumbent_offer(const DP &p, const Tree<row_t, BIG> &t, int g, u
     wave_sync();
     if (!better) return;
     u16 *action = rec.action();
-    const u16 *played = rec.played();
-    for (int q = lane; q < prefix && q < p.N; q += 64) action[q] = played[q];
-    if (lane < depth && prefix + lane < p.N) action[prefix + lane] = t.pAct[t.hdr[pn0].prior_off + t.vis[pe0].idx];
-    if (BIG && lane + 64 < depth && prefix + lane + 64 < p.N) action[prefix + lane + 64] = t.pAct[t.hdr[pn1].prior_off + t.vis[pe1].idx];
+    incumbent_lead(p, t, rec, prefix, depth, pe0, pn0, pe1, pn1);
     int moves = prefix + depth;
     if (extra >= 0) {
         if (lane == 0 && moves < p.N) action[moves] = (u16)extra;
@@ -1057,6 +1069,7 @@ __device__ void incumbent_offer(const DP &p, const Tree<row_t, BIG> &t, int g, u
     if (lane == 0) {
         *rec.score() = r;
         meta[0] = (int)t.hdr[node].term; meta[1] = moves; meta[2] = prefix; meta[3] = updates;
+        if (p.inc_src) { p.inc_src[2 * g] = moves; p.inc_src[2 * g + 1] = -1; }  // a tree terminal: reached after all of its moves, no playout
     }
     wave_sync();
 }
@@ -1067,6 +1080,7 @@ __device__ __forceinline__ void incumbent_reset(const DP &p, int g) {
         *rec.score() = 0.0; p.inc_new[g].node = NONE32;
         int *m = rec.meta();
         m[0] = 0; m[1] = -1; m[2] = 0; m[3] = 0;
+        if (p.inc_src) { p.inc_src[2 * g] = 0; p.inc_src[2 * g + 1] = -1; }
     }
 }
 
@@ -1110,6 +1124,7 @@ __device__ void finish_episode_impl(const DP &p, Tree<row_t, BIG> &t, int g, con
         if (lane < p.H) dst.board()[lane] = src.board()[lane];
         if (lane < 4) dst.meta()[lane] = src.meta()[lane];
         if (lane == 0) *dst.score() = *src.score();
+        if (p.inc_src && lane < 2) p.inc_src[2 * ((size_t)p.G + idx) + lane] = p.inc_src[2 * g + lane];
     }
     if (p.tr_action) {  // the episode's trace and final bin, at the ring index of its record
         if (idx < p.fin_cap) {
@@ -2485,7 +2500,8 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_game_ended(DP p, long 
 // draws from h0 = mix64(key_hash(S, seed) ^ e): at step s it plays legal move number umulhi(sample_u64(h0, j, s), nv) in ascending
 // action order until no legal move is left -- every move places one item, so N steps bound the loop -- and its outcome is the final
 // bin's ranked reward against the slot's R2 threshold, the r == bl tie resolved by tie_value as the search resolves Es.  A function
-// of (state, items, episode id, threshold, seed, tie salt) only: not of the slot, the evaluator row or the launch shape.
+// of (state, items, episode id, threshold, seed, tie salt) only: not of the slot, the evaluator row or the launch shape -- which is what
+// lets a playout be played a second time to record its moves (playout_offer) instead of recording all of them.
 // One wave per playout.  gen_valid_moves with neither list nor mask leaves the per-item column masks in the wave's VM_WORDS LDS
 // words; lanes = items then find the picked move with a popcount prefix and an n-th set bit on the owning item's mask, so the action
 // list is never written.  Returns the final state through myrow / rem0 / rem1 and the number of moves played.
@@ -2498,8 +2514,11 @@ template <bool BIG> __device__ __forceinline__ ItemSizes load_item_sizes(const u
     if (BIG && lane + 64 < N) { z.w_hi = wh[2 * (lane + 64)]; z.h_hi = wh[2 * (lane + 64) + 1]; }
     return z;
 }
-template <typename row_t, bool BIG>
-__device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row_t &myrow, u64 &rem0, u64 &rem1, u64 h0, u64 j, u64 *vm) {
+// REC: step s also stores its action, item * W + column, in act_out[s] while s < act_cap (lane 0, a plain vector store); without REC
+// the sink is not looked at and the code is what it was before the sink existed.
+template <typename row_t, bool BIG, bool REC = false>
+__device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row_t &myrow, u64 &rem0, u64 &rem1, u64 h0, u64 j, u64 *vm, u16 *act_out = nullptr,
+                              int act_cap = 0) {
     const int lane = lane_id(), N = p.N;
     const bool big = BIG && N > 64;
     ValidSink sink;
@@ -2530,6 +2549,7 @@ __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row
         }
         for (int k = 0; k < skip; ++k) own &= own - 1;  // skip < popcount(own) <= 64
         const int col = __ffsll((long long)own) - 1;
+        if (REC && lane == 0 && s < act_cap) act_out[s] = (u16)(item * p.W + col);
         const int w = item < 64 ? __builtin_amdgcn_readlane(z.w_lo, item & 63) : __builtin_amdgcn_readlane(z.w_hi, item & 63);
         const int h = item < 64 ? __builtin_amdgcn_readlane(z.h_lo, item & 63) : __builtin_amdgcn_readlane(z.h_hi, item & 63);
         myrow = apply_move_rows<row_t>(myrow, p.H, p.W, col, w, h);
@@ -2546,10 +2566,58 @@ __device__ int playout_outcome(const DP &p, row_t myrow, u64 rem0, u64 rem1, int
     return e;
 }
 
+// The playout offer of slot g's waiting leaf (rp_set_incumbent_playouts): playout j scored r, the largest score of the leaf's playouts
+// and the lowest index among equals.  It replaces the slot's incumbent under the rule of the tree offers (incumbent_offer): none yet, or
+// strictly greater -- so the same leaf offered twice changes nothing.  The winner is then played again from the leaf, a function of
+// (h0, j) alone, with the action sink pointed behind the head of the list (played moves, then the leaf's path as k_search stored it for
+// the commit), and its final state is the record's board and outcome.  One wave, all lanes; every lane holds the same r and j.
+template <typename row_t, bool BIG>
+__device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
+    const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
+    const int lane = lane_id();
+    int *meta = rec.meta();
+    const int have = uni(meta[1]), updates = uni(meta[3]) + 1;
+    const bool better = uni((int)(have < 0 || r > *rec.score())) != 0;
+    wave_sync();
+    if (!better) return;
+    const int prefix = uni(p.moves[g]);
+    int depth = uni(p.path_len[g]);
+    if (depth < 0 || depth > p.N) depth = 0;
+    const u32 *pe = p.path_edge + (size_t)g * p.N, *pn = p.path_node + (size_t)g * p.N;
+    u32 pe0 = NONE32, pn0 = NONE32, pe1 = NONE32, pn1 = NONE32;
+    if (lane < depth) { pe0 = pe[lane]; pn0 = pn[lane]; }
+    if (BIG && lane + 64 < depth) { pe1 = pe[lane + 64]; pn1 = pn[lane + 64]; }
+    const int tree_moves = prefix + depth;
+    // the leaf, its items and its stream are loaded again here: an offer that enters is rare, and nothing of the playout loop's state has
+    // to stay in registers across the barrier for it
+    const Tree<row_t, BIG> t(p, g);
+    row_t myrow; u64 rem0, rem1;
+    t.load_key(p.leaf_node[g], myrow, rem0, rem1);
+    const ItemSizes z = load_item_sizes<BIG>(t.wh, p.N);
+    const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ p.episode[g]);
+    const int room = tree_moves < p.N ? p.N - tree_moves : 0;  // every move places one item: the list never outgrows N
+    const int m = random_playout<row_t, BIG, true>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, vm, rec.action() + (tree_moves < p.N ? tree_moves : 0), room);
+    double r_again;
+    const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r_again);
+    incumbent_lead(p, t, rec, prefix, depth, pe0, pn0, pe1, pn1);
+    if (lane < p.H) rec.board()[lane] = (u64)myrow;
+    if (lane == 0) {
+        *rec.score() = r_again;
+        meta[0] = e; meta[1] = tree_moves + m; meta[2] = prefix; meta[3] = updates;
+        p.inc_src[2 * g] = tree_moves; p.inc_src[2 * g + 1] = j;
+    }
+    wave_sync();
+}
+
 // Leaves waiting for evaluation -> v[b] = float32(sum of K outcomes) / float32(K), and pi row b = 1 / A when pi != NULL.  One workgroup
 // per evaluator row (the mapping of k_leaf_planes), its waves take playouts wave, wave + WAVES_PER_BLOCK, ...; the outcomes are summed
 // as integers through LDS behind one barrier.  Every exit condition depends on the row alone, so it is workgroup-uniform.
-template <typename row_t, bool BIG>
+// TRACK (playout incumbents on, rp_set_incumbent_playouts): every wave also keeps its best (score, playout) -- its playout indices
+// ascend, so strictly greater keeps the lowest -- and behind the same barrier wave 0 reduces them and makes the leaf's one offer
+// (playout_offer).  The host chooses the instantiation, one uniform branch per launch: as a run-time branch inside one kernel the offer
+// took k_rollout from 8 waves per SIMD to 7 and made it spill scalar registers with the mode off too (make resource-usage), so the
+// kernel of the mode that is off stays the code it was.
+template <typename row_t, bool BIG, bool TRACK>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int playouts, float *pi, float *v, long long capacity_rows) {
     const int b = blockIdx.x, wv = wave_in_block();
     if (b >= (p.rows_identity ? p.G : *p.eval_count) || b >= capacity_rows) return;
@@ -2557,6 +2625,8 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
     if (p.phase[g] != RP_PHASE_WAIT_EVAL) return;
     __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
     __shared__ int s_sum[WAVES_PER_BLOCK];
+    __shared__ double s_best_r[TRACK ? WAVES_PER_BLOCK : 1];  // the reduction words of the offer; not allocated unless used
+    __shared__ int s_best_j[TRACK ? WAVES_PER_BLOCK : 1];
     Tree<row_t, BIG> t(p, g);
     row_t leaf; u64 l0, l1;
     t.load_key(p.leaf_node[g], leaf, l0, l1);
@@ -2565,14 +2635,19 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
     const bool has_buf = p.has_buf[g] != 0;
     const double bl = p.bl[g];
     const u64 h0 = mix64(key_hash<row_t>(leaf, p.H, p.N, l0, l1, p.seed) ^ p.episode[g]);
-    int sum = 0;
+    int sum = 0, best_j = -1;
+    double best_r = 0.0;
     for (int j = wv; j < playouts; j += WAVES_PER_BLOCK) {
         row_t myrow = leaf; u64 rem0 = l0, rem1 = l1;
         random_playout<row_t, BIG>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
         double r;
         sum += playout_outcome<row_t>(p, myrow, rem0, rem1, area, max_h, has_buf, bl, &r);
+        if (TRACK && (best_j < 0 || r > best_r)) { best_r = r; best_j = j; }
     }
-    if (lane_id() == 0) s_sum[wv] = sum;
+    if (lane_id() == 0) {
+        s_sum[wv] = sum;
+        if (TRACK) { s_best_r[wv] = best_r; s_best_j[wv] = best_j; }
+    }
     if (pi) {
         const float u = 1.0f / (float)p.A;
         float *row = pi + (size_t)b * p.A;
@@ -2584,6 +2659,37 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
         for (int k = 0; k < WAVES_PER_BLOCK; ++k) tot += s_sum[k];
         v[b] = (float)tot / (float)playouts;
     }
+    if (TRACK && wv == 0) {  // wave 0 plays playout 0, so it always has a candidate
+        double r = s_best_r[0];
+        int j = s_best_j[0];
+        for (int k = 1; k < WAVES_PER_BLOCK; ++k) {
+            const double rk = s_best_r[k];
+            const int jk = s_best_j[k];
+            if (jk >= 0 && (rk > r || (rk == r && jk < j))) { r = rk; j = jk; }
+        }
+        playout_offer<row_t, BIG>(p, g, r, uni(j), s_vm[0]);
+    }
+}
+// The action lists of the playouts k_rollout_states plays, through the recording path of the playout offers: one wave per (state,
+// playout), zeros past the playout's moves.
+template <typename row_t, bool BIG>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_paths(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh, const u64 *episode,
+                                                                         u16 *action, int *moves_out) {
+    const long long idx = (long long)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
+    if (idx >= B * playouts) return;
+    const long long b = idx / playouts;
+    const int j = (int)(idx - b * playouts), lane = lane_id();
+    __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
+    row_t myrow; u64 rem0, rem1;
+    load_host_state<row_t>(p, rows + b * p.H, rem + b * p.N, myrow, rem0, rem1);
+    const u8 *w2 = wh + b * p.N * 2;
+    const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
+    const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
+    u16 *mine = action + idx * p.N;
+    const int moves = random_playout<row_t, BIG, true>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()], mine, p.N);
+    for (int q = lane; q < p.N; q += 64)
+        if (q >= moves) mine[q] = (u16)0;
+    if (lane == 0) moves_out[idx] = moves;
 }
 // The stateless batch form: one wave per (state, playout) of B host states, K playouts each.
 template <typename row_t, bool BIG>
@@ -4351,6 +4457,7 @@ struct rp_ctx {
     // incumbent records (rp_set_incumbent): the same life cycle
     u8 *inc = nullptr, *fin_inc = nullptr;
     IncNew *inc_new = nullptr;
+    int *inc_src = nullptr;  // rp_set_incumbent_playouts
 };
 
 static std::string g_create_error;
@@ -5079,8 +5186,11 @@ extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, flo
     const DP &d = ctx->d;
     long long rows = std::min<long long>(capacity_rows, d.G);
     if (rows == 0) return RP_OK;
-    return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev, v_dev,
-                  capacity_rows);
+    if (d.inc_src)  // playout incumbents: the instantiation that also makes each leaf's offer
+        return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag, true>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev,
+                      v_dev, capacity_rows);
+    return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag, false>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev,
+                  v_dev, capacity_rows);
 }
 
 extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
@@ -5113,6 +5223,29 @@ extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, c
     if (rc == RP_OK)
         rc = launch_waves(ctx, "k_rollout_states", GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag>), (long long)n, d, B, playouts, drows, drem, dwh, darea, dmh,
                           dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
+    return rc == RP_OK ? s.finish() : rc;
+}
+
+extern "C" int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh, const uint64_t *episode_id,
+                                int32_t playouts, uint16_t *action_out, int32_t *moves_out) {
+    if (!ctx || B < 0 || !rows || !remaining || !item_wh || !action_out || !moves_out) return fail(ctx, RP_ERR_ARG, "rp_rollout_paths: bad argument");
+    if (playouts < 1 || playouts > RP_MAX_PLAYOUTS) return fail(ctx, RP_ERR_ARG, "rp_rollout_paths: playouts %d outside 1..%d", playouts, RP_MAX_PLAYOUTS);
+    if (B == 0) return RP_OK;
+    const DP &d = ctx->d;
+    const size_t n = (size_t)B * (size_t)playouts;
+    if (n > (size_t)0x7FFFFFFF) return fail(ctx, RP_ERR_ARG, "rp_rollout_paths: %lld states x %d playouts exceed 2^31 - 1", (long long)B, playouts);
+    if (item_sizes(ctx, "rp_rollout_paths", B, item_wh, nullptr, nullptr) != RP_OK) return RP_ERR_ARG;
+    Scratch s(ctx);
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    u64 *dep = episode_id ? s.in((const u64 *)episode_id, (size_t)B) : nullptr;
+    u16 *dact = s.out((u16 *)action_out, n * d.N);
+    int *dmoves = s.out(moves_out, n);
+    int rc = s.ok();
+    if (rc == RP_OK)
+        rc = launch_waves(ctx, "k_rollout_paths", GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag>), (long long)n, d, B, playouts, drows, drem, dwh, dep, dact,
+                          dmoves);
     return rc == RP_OK ? s.finish() : rc;
 }
 
@@ -5225,6 +5358,7 @@ struct BestOut {
     int32_t *outcome = nullptr, *moves = nullptr, *prefix = nullptr, *updates = nullptr;
     uint16_t *action = nullptr;
     uint64_t *board = nullptr;
+    int32_t *tree_moves = nullptr, *playout = nullptr;  // rp_pop_finished_best_playouts: from the side array, not from the records
     bool any() const { return score || outcome || moves || prefix || updates || action || board; }
 };
 // n incumbent records in host memory -> the caller's arrays; a record without an incumbent: moves = -1, zeros elsewhere
@@ -5272,7 +5406,54 @@ extern "C" int rp_set_incumbent(rp_ctx *ctx, int32_t enable) {
     d.fin_inc = enable ? ctx->fin_inc : nullptr;
     d.inc_new = enable ? ctx->inc_new : nullptr;
     d.inc_stride = (int)IncRec::stride(d.H, d.N);
+    if (!enable) d.inc_src = nullptr;  // playout incumbents go with the incumbents
     return RP_OK;
+}
+
+extern "C" int rp_set_incumbent_playouts(rp_ctx *ctx, int32_t enable) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_incumbent_playouts: bad argument");
+    DP &d = ctx->d;
+    if (!d.inc) return fail(ctx, RP_ERR_STATE, "rp_set_incumbent_playouts: incumbents are off (rp_set_incumbent(ctx, 1) first)");
+    {   // not while episodes are being played: the leaves they have already evaluated would be missing
+        std::vector<int> ph((size_t)d.G);
+        HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int g = 0; g < d.G; ++g)
+            if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY)
+                return fail(ctx, RP_ERR_STATE, "rp_set_incumbent_playouts: slot %d is in the middle of an episode; switch between pools", g);
+    }
+    if (enable && !ctx->inc_src) {  // 8 (G + fin_cap) bytes, once
+        const size_t n = (size_t)d.G + (size_t)d.fin_cap;
+        int *src = nullptr;
+        ALLOC(ctx, src, 2 * n);
+        std::vector<int> none(2 * n, 0);  // (0, -1): no record is a playout's before its episode begins
+        for (size_t k = 0; k < n; ++k) none[2 * k + 1] = -1;
+        HIPCHK(ctx, hipMemcpyAsync(src, none.data(), none.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->inc_src = src;
+    }
+    d.inc_src = enable ? ctx->inc_src : nullptr;
+    return RP_OK;
+}
+
+// n (tree_moves, playout) pairs in host memory -> the caller's arrays
+static void unpack_sources(const int *src, size_t n, int32_t *tree_moves_out, int32_t *playout_out) {
+    for (size_t k = 0; k < n; ++k) {
+        if (tree_moves_out) tree_moves_out[k] = src[2 * k];
+        if (playout_out) playout_out[k] = src[2 * k + 1];
+    }
+}
+
+extern "C" int rp_incumbent_sources(rp_ctx *ctx, int32_t first, int32_t count, int32_t *tree_moves_out, int32_t *playout_out) {
+    if (!ctx || first < 0 || count < 0 || first + count > ctx->d.G) return fail(ctx, RP_ERR_ARG, "rp_incumbent_sources: bad argument");
+    const DP &d = ctx->d;
+    if (!d.inc_src) return fail(ctx, RP_ERR_ARG, "rp_incumbent_sources: playout incumbents are off (rp_set_incumbent_playouts(ctx, 1) before the episodes begin)");
+    if (count == 0) return RP_OK;
+    std::vector<int> buf(2 * (size_t)count);
+    HIPCHK(ctx, hipMemcpyAsync(buf.data(), d.inc_src + 2 * (size_t)first, buf.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unpack_sources(buf.data(), (size_t)count, tree_moves_out, playout_out);
+    return check_device_error(ctx);
 }
 
 // Running incumbents of slots first .. first + count - 1: host copies; moves = -1 (and zeros elsewhere) where the episode has none yet.
@@ -5639,8 +5820,14 @@ static int pop_finished(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, in
         inc.resize((size_t)n * d.inc_stride);
         HIPCHK(ctx, hipMemcpyAsync(inc.data(), d.fin_inc + off * d.inc_stride, inc.size(), hipMemcpyDeviceToHost, ctx->stream));
     }
+    std::vector<int> src;
+    if (best.tree_moves || best.playout) {
+        src.resize(2 * (size_t)n);
+        HIPCHK(ctx, hipMemcpyAsync(src.data(), d.inc_src + 2 * ((size_t)d.G + off), src.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (best.any()) unpack_incumbents(d, inc.data(), (size_t)n, best);
+    if (!src.empty()) unpack_sources(src.data(), (size_t)n, best.tree_moves, best.playout);
     ctx->fin_popped += n;
     if (ctx->fin_popped == cnt) {  // ring drained: rewind
         HIPCHK(ctx, hipMemsetAsync(d.fin_count, 0, sizeof(int), ctx->stream));
@@ -5674,6 +5861,22 @@ extern "C" int rp_pop_finished_best(rp_ctx *ctx, int64_t max_n, uint64_t *episod
     BestOut best;
     best.score = best_score_out; best.outcome = best_outcome_out; best.moves = best_moves_out; best.prefix = best_prefix_out;
     best.updates = best_updates_out; best.action = best_action_out; best.board = best_board_out;
+    return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out, best);
+}
+
+extern "C" int rp_pop_finished_best_playouts(rp_ctx *ctx, int64_t max_n, uint64_t *episode_id_out, int32_t *outcome_out, double *score_out, int32_t *moves_out,
+                                             uint16_t *action_out, uint64_t *rows_out, uint64_t *board_out, double *best_score_out, int32_t *best_outcome_out,
+                                             int32_t *best_moves_out, int32_t *best_prefix_out, int32_t *best_updates_out, uint16_t *best_action_out,
+                                             uint64_t *best_board_out, int32_t *best_tree_moves_out, int32_t *best_playout_out, int64_t *n_out) {
+    if (!ctx || max_n < 0 || !n_out) return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best_playouts: bad argument");
+    if (!ctx->d.inc_src)
+        return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best_playouts: playout incumbents are off (rp_set_incumbent_playouts(ctx, 1) before the pool begins)");
+    if ((action_out || rows_out || board_out) && !ctx->d.tr_action)
+        return fail(ctx, RP_ERR_ARG, "rp_pop_finished_best_playouts: a trace output was requested while the placement trace is off (rp_set_trace)");
+    BestOut best;
+    best.score = best_score_out; best.outcome = best_outcome_out; best.moves = best_moves_out; best.prefix = best_prefix_out;
+    best.updates = best_updates_out; best.action = best_action_out; best.board = best_board_out;
+    best.tree_moves = best_tree_moves_out; best.playout = best_playout_out;
     return pop_finished(ctx, max_n, episode_id_out, outcome_out, score_out, moves_out, action_out, rows_out, board_out, n_out, best);
 }
 

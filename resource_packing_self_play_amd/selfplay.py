@@ -43,6 +43,8 @@ class _Group:
             self.eng.set_trace(True)
         if owner.record_best:
             self.eng.set_incumbent(True)
+        if owner.playout_incumbents:
+            self.eng.set_incumbent_playouts(True)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         self.wide_logits = owner.wide_logits
@@ -125,7 +127,8 @@ class _Group:
 class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
-                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False):
+                 tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False,
+                 playout_incumbents=False):
         """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
         uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
         or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
@@ -135,8 +138,11 @@ class BatchedSelfPlay:
         record_packings: the engines record every move's placement (rp_set_trace); run() / run_from_seeds() return what they always
         return and the finished episodes' layouts are collected for pop_packings().
         record_best: the engines keep every episode's incumbent (rp_set_incumbent) -- the best complete packing its search tree saw,
-        which the played one cannot beat; the finished episodes' incumbents are collected for pop_best_packings().  Tree terminals only:
-        the playouts of evaluator="rollout" do not feed it.
+        which the played one cannot beat; the finished episodes' incumbents are collected for pop_best_packings().  Tree terminals only,
+        unless playout_incumbents is on.
+        playout_incumbents: with record_best and evaluator="rollout", every playout is a candidate too (rp_set_incumbent_playouts): each
+        evaluated leaf offers its best playout, and an incumbent's `tree_moves` / `playout` say where it came from.  ValueError
+        without record_best or with another evaluator.
         host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
         eagerly with one host round trip each.  tie_salt: salt of the deterministic `r == bl` tie (default: derived from seed)."""
@@ -167,6 +173,9 @@ class BatchedSelfPlay:
         self.wide_logits = bool(wide_logits)
         self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
         self.record_best = bool(record_best)  # likewise
+        self.playout_incumbents = bool(playout_incumbents)  # likewise
+        if self.playout_incumbents and not (self.record_best and rollout):
+            raise ValueError("playout_incumbents needs record_best=True and evaluator='rollout'")
         self._packings = []
         self._best = []
         self._pool_items = None
@@ -265,11 +274,18 @@ class BatchedSelfPlay:
         self._packings = []
         self.invalidate_graph()
 
-    def set_record_best(self, on=True):
-        """Switches the incumbents of every group between pools (refused while episodes are being played); re-captures the waves."""
+    def set_record_best(self, on=True, playout_incumbents=False):
+        """Switches the incumbents of every group between pools (refused while episodes are being played); re-captures the waves.
+        playout_incumbents: the playouts of evaluator="rollout" are candidates too (ValueError with `on` false or another evaluator);
+        switching the incumbents off switches it off."""
+        if playout_incumbents and not (on and self.evaluator == "rollout"):
+            raise ValueError("playout_incumbents needs record_best on and evaluator='rollout'")
         for g in self.groups:
             g.eng.set_incumbent(on)
+            if on:
+                g.eng.set_incumbent_playouts(playout_incumbents)
         self.record_best = bool(on)
+        self.playout_incumbents = bool(playout_incumbents)
         self._best = []
         self.invalidate_graph()
 
@@ -426,6 +442,8 @@ class BatchedSelfPlay:
                 raise RuntimeError("episode %d: the incumbent's actions replay to another bin than the engine recorded" % int(ids[k]))
             p = Packing(int(ids[k]), self.W, items[i], actions, rows, board, int(best["outcome"][k]), float(best["score"][k]), **start)
             p.prefix, p.updates = int(best["prefix"][k]), int(best["updates"][k])
+            if "playout" in best:  # playout incumbents: where the record came from
+                p.tree_moves, p.playout = int(best["tree_moves"][k]), int(best["playout"][k])
             self._best.append(p)
 
     def _keep_packings(self, ids, outcome, score, moves, action, rows, board):

@@ -32,8 +32,10 @@ class Packing:
     An incumbent (pack(..., best=True), BatchedSelfPlay.pop_best_packings) is a Packing too: the best complete packing the episode's search
     tree saw.  It also carries prefix (how many of its moves had been played when the search found it), updates (how often the episode's
     incumbent was replaced, the first entry included) and played (the Packing the move rule played, where it was recorded); all three
-    are None on a played Packing."""
-    prefix = updates = played = None
+    are None on a played Packing.  Under playout incumbents (pack(..., playout_incumbents=True)) it also says where it came from:
+    tree_moves (the number of actions after which the search tree was left) and playout (the index of the random playout that made the
+    remaining moves, -1 for a terminal of the tree, whose tree_moves == moves); None otherwise."""
+    prefix = updates = played = tree_moves = playout = None
 
     def __init__(self, episode_id, W, item_wh, actions, rows, board, outcome=0, score=0.0, initial_board=None, present=None):
         self.episode_id = int(episode_id)
@@ -303,7 +305,7 @@ def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin
 
 
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
-         driver=None, seed=0, initial_board=None, remaining=None, best=False, **driver_kw):
+         driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
@@ -325,18 +327,25 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     an empty list every outcome is +1 and the search is blind, so a network-free solve wants a buffer -- random_scores() gives one.
     best: return every instance's incumbent instead of the packing that was played: the best complete packing the episode's search tree
     saw (rp_set_incumbent; the first found among equals), with `prefix`, `updates` and `played` -- the played Packing -- set.  Its own
-    final state is in every episode's tree, so best.score >= best.played.score always.  Tree terminals only: the playouts of
-    evaluator="rollout" are not candidates.  A driver passed in must have been built with record_best=True."""
+    final state is in every episode's tree, so best.score >= best.played.score always.  Tree terminals only, unless playout_incumbents
+    is on.  A driver passed in must have been built with record_best=True.
+    playout_incumbents (with best and evaluator="rollout"): every random playout the search runs is a candidate too
+    (rp_set_incumbent_playouts) -- in a network-free search they are nearly all the finished packings it ever computes; the incumbents
+    then carry `tree_moves` and `playout`.  A driver passed in must have been built with the same setting."""
     from .selfplay import BatchedSelfPlay
     _check_instances(item_wh, seeds, initial_board, remaining)
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
+    if playout_incumbents and not best:
+        raise ValueError("playout_incumbents is a property of the incumbents: it needs best=True")
     if sp is None:
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
         sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
-                             **driver_kw)
+                             playout_incumbents=bool(playout_incumbents), **driver_kw)
+    elif sp.playout_incumbents != bool(playout_incumbents):
+        raise RuntimeError("the driver was built with playout_incumbents=%r" % sp.playout_incumbents)
     elif sp.move_rule != rule:
         sp.set_move_rule(rule)
     try:
