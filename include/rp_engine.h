@@ -40,7 +40,8 @@ extern "C" {
                              8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states)
                              9: initial states of pool instances (rp_set_instance_initial)
                              10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents); additive, same number: playout
-                                 incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths) */
+                                 incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths) and the
+                                 playout policy (rp_set_playout_policy, rp_playout_policy) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -357,6 +358,30 @@ int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_
 int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
                      const uint64_t *episode_id /* NULL: 0 */, int32_t playouts, uint16_t *action_out /*[B][playouts][N]*/,
                      int32_t *moves_out /*[B][playouts]*/);
+/* The playout policy of the context: how a playout (MCTS_bpp.py:87) chooses among the legal moves (getValidMoves,
+ * BinPackingGame.py:78-92).  Two small integer powers (w_pow, h_pow); a legal move of item i with size (w_i, h_i) gets the integer
+ * weight wt_i = w_i^w_pow * h_i^h_pow.  The default (0, 0) is the uniform rule above.  The sampling rule:
+ *   - At step s of playout j, m_i is the legal-column mask of item i and c_i = popcount(m_i).
+ *   - nv = sum c_i == 0 ends the playout.
+ *   - Otherwise T = sum c_i * wt_i.
+ *   - pick = umulhi(sample(h0, j, s), T), the same stream: h0 = mix64(key_hash(S, seed) ^ e).
+ *   - The legal moves lie in ascending action order (a = item * W + column).  Each move occupies wt_i consecutive units of [0, T).
+ *     The move that owns unit `pick` is played:
+ *       item   = the first i whose inclusive sum sum_{k<=i} c_k wt_k exceeds pick;
+ *       column = set bit number floor((pick - sum_{k<i} c_k wt_k) / wt_i) of m_i, counted from 0.
+ *   - Limits: w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2.  Then 1 <= wt_i <= 4096 and T <= 64 * 128 * 4096 = 2^25, so the sums stay
+ *     in 32 bits.
+ *   - With (0, 0) the rule is the uniform one, bit for bit.
+ * Everything else about a playout is unchanged: its outcome, its score, the tie rule, the independence from slot, row and launch, and the
+ * bound of N steps.  The weights look at the item alone -- not at the column or the height the move would reach -- so they are a
+ * function of the episode's items and cost no state per slot.
+ * RP_ERR_ARG outside the limits; RP_ERR_STATE while any slot is in the middle of an episode (an incumbent's record would stop being a
+ * function of the search alone: a playout offer is replayed under the policy that scored it).  Applies to rp_rollout_eval,
+ * rp_rollout_states, rp_rollout_paths and the playout offers from then on.  Kernel arguments are baked into captured graphs:
+ * re-capture after switching. */
+int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow);
+/* The powers in force (either pointer may be NULL). */
+int rp_playout_policy(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out);
 
 /* ---- results ------------------------------------------------------------------------- */
 /* counts[a] = Nsa[(root, a)] (MCTS_bpp.py:40-41), host buffer [count][W*N] */

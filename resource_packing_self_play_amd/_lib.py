@@ -67,6 +67,8 @@ _SIGS = {
     "rp_incumbents": (C.c_int, [_vp, _i32, _i32] + [_vp] * 7),
     "rp_set_incumbent_playouts": (C.c_int, [_vp, _i32]),
     "rp_incumbent_sources": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "rp_set_playout_policy": (C.c_int, [_vp, _i32, _i32]),
+    "rp_playout_policy": (C.c_int, [_vp, _vp, _vp]),
     "rp_last_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_search_step": (C.c_int, [_vp, _vp]),
     "rp_leaf_planes": (C.c_int, [_vp, _vp, _i64]),
@@ -117,6 +119,28 @@ _SIGS = {
     "rp_selftest_softmax": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
 }
 _lib = None
+
+# names of the playout policies (rp_set_playout_policy): the powers (w_pow, h_pow) of an item's move weight w^w_pow * h^h_pow
+PLAYOUT_POLICIES = {"uniform": (0, 0), "area": (1, 1), "width": (1, 0), "width2": (2, 0), "height": (0, 1), "height2": (0, 2)}
+
+
+def playout_policy_powers(policy):
+    """A playout policy as its pair of powers: one of PLAYOUT_POLICIES' names, or a pair of integers (w_pow, h_pow) with w_pow >= 0,
+    h_pow >= 0 and w_pow + h_pow <= 2; None is uniform.  ValueError for anything else."""
+    if policy is None:
+        return 0, 0
+    if isinstance(policy, str):
+        if policy not in PLAYOUT_POLICIES:
+            raise ValueError("unknown playout policy %r: one of %s, or a pair (w_pow, h_pow)" % (policy, ", ".join(sorted(PLAYOUT_POLICIES))))
+        return PLAYOUT_POLICIES[policy]
+    try:
+        w_pow, h_pow = policy
+        ok = all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (w_pow, h_pow))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or w_pow < 0 or h_pow < 0 or w_pow + h_pow > 2:
+        raise ValueError("playout policy %r: a name or a pair of integers (w_pow, h_pow), w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2" % (policy,))
+    return int(w_pow), int(h_pow)
 
 
 def load():
@@ -334,6 +358,18 @@ class Engine:
         is in mid-episode; re-capture graphs after switching.  pop_finished(best=True) then also returns tree_moves / playout."""
         self._ck(self.L.rp_set_incumbent_playouts(self.h, 1 if on else 0))
         self.incumbent_playouts = bool(on)
+
+    def set_playout_policy(self, w_pow, h_pow):
+        """Playout policy (rp_set_playout_policy): a legal move of an item (w, h) weighs w^w_pow * h^h_pow in every playout of
+        rollout_eval, rollout_states, rollout_paths and the playout offers; (0, 0) is uniform.  Refused outside w_pow, h_pow >= 0,
+        w_pow + h_pow <= 2 and while a slot is in mid-episode; re-capture graphs after switching."""
+        self._ck(self.L.rp_set_playout_policy(self.h, int(w_pow), int(h_pow)))
+
+    def playout_policy(self):
+        """The powers (w_pow, h_pow) in force (rp_playout_policy)."""
+        w, h = _i32(0), _i32(0)
+        self._ck(self.L.rp_playout_policy(self.h, C.byref(w), C.byref(h)))
+        return int(w.value), int(h.value)
 
     def incumbent_sources(self, first=0, count=None):
         """Where the running incumbents came from (rp_incumbent_sources) -> dict of tree_moves / playout i32 [n]: the actions after which
@@ -579,12 +615,13 @@ class Engine:
     MAX_PLAYOUTS = 256  # rp_rollout_eval / rp_rollout_states
 
     def rollout_eval(self, v_ptr, capacity_rows, playouts, pi_ptr=None):
-        """Random-playout evaluator of the waiting leaves (rp_rollout_eval): v[b] = mean outcome of `playouts` uniform random playouts,
-        and -- with pi_ptr -- pi row b = 1 / A.  Device pointers of capacity_rows rows; enqueues only."""
+        """Random-playout evaluator of the waiting leaves (rp_rollout_eval): v[b] = mean outcome of `playouts` random playouts -- uniform
+        over the legal moves, or weighted by the item under set_playout_policy -- and, with pi_ptr, pi row b = 1 / A.  Device pointers of
+        capacity_rows rows; enqueues only."""
         self._ck(self.L.rp_rollout_eval(self.h, int(playouts), C.c_void_p(pi_ptr) if pi_ptr else None, C.c_void_p(v_ptr), int(capacity_rows)))
 
     def rollout_states(self, rows, remaining, item_wh, total_area, max_h, rewards, alpha, playouts, episode_id=None, boards=True):
-        """`playouts` uniform random playouts from each of B host states (rp_rollout_states) -> (outcome int32 [B, K], score float64
+        """`playouts` random playouts (uniform, or under set_playout_policy) from each of B host states (rp_rollout_states) -> (outcome int32 [B, K], score float64
         [B, K], moves int32 [B, K], final bins uint64 [B, K, H] or None without `boards`)."""
         rows = _arr(rows, np.uint64); B = rows.shape[0]; K = int(playouts)
         rows = _arr(rows, np.uint64, (B, self.H)); remaining = _arr(remaining, np.uint8, (B, self.N))

@@ -208,6 +208,9 @@ struct DP {  // device view of a context, passed by value to every kernel
     // playout incumbents (rp_set_incumbent_playouts): where each record came from, (tree_moves, playout) per slot and, behind them, per
     // ring entry.  NULL while the mode is off: k_rollout then takes one uniform branch and the tree offers write nothing more.
     int *inc_src;  // [G + fin_cap][2]
+    // playout policy (rp_set_playout_policy): a legal move of an item (w, h) weighs w^pol_w * h^pol_h in every playout.  (0, 0) =
+    // uniform: the host then launches the instantiations that never read the pair.
+    int pol_w, pol_h;
 };
 // the first error of a launch sequence is the one reported (later ones are usually its consequences)
 __device__ __forceinline__ void set_error(const DP &p, int code) { atomicCAS(p.error, 0, code); }
@@ -2514,9 +2517,19 @@ template <bool BIG> __device__ __forceinline__ ItemSizes load_item_sizes(const u
     if (BIG && lane + 64 < N) { z.w_hi = wh[2 * (lane + 64)]; z.h_hi = wh[2 * (lane + 64) + 1]; }
     return z;
 }
+// b^e for the playout policy's powers, e in 0..2 (rp_set_playout_policy)
+__device__ __forceinline__ int policy_power(int b, int e) { return e == 0 ? 1 : e == 1 ? b : b * b; }
+__device__ __forceinline__ int policy_weight(int w, int h, int pol_w, int pol_h) { return policy_power(w, pol_w) * policy_power(h, pol_h); }
 // REC: step s also stores its action, item * W + column, in act_out[s] while s < act_cap (lane 0, a plain vector store); without REC
 // the sink is not looked at and the code is what it was before the sink existed.
-template <typename row_t, bool BIG, bool REC = false>
+// WT: the playout policy of the context (rp_set_playout_policy, p.pol_w / p.pol_h not both 0).  A legal move of item i weighs
+// wt_i = w_i^pol_w * h_i^pol_h, 1 <= wt_i <= 4096 as the powers sum to 2 at most, and the moves, in ascending action order, each own wt_i
+// consecutive units of [0, T), T = sum popcount(m_i) * wt_i <= 64 * 128 * 4096 = 2^25: the scans stay in 32 bits.  The move that owns
+// unit pick = umulhi(sample, T) is played: item = the first whose inclusive sum of popcount * wt exceeds pick, column = its set bit
+// number (pick - the sum before it) / wt_i -- one division of wave-uniform values.  The weights depend on the item alone, so they are
+// one register per lane (two for N > 64), set before the loop.  T needs both halves' scans before the draw; the uniform form knows
+// its total, nv, from gen_valid_moves and scans the second half only when the pick falls there.  Without WT this is the uniform code.
+template <typename row_t, bool BIG, bool REC = false, bool WT = false>
 __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row_t &myrow, u64 &rem0, u64 &rem1, u64 h0, u64 j, u64 *vm, u16 *act_out = nullptr,
                               int act_cap = 0) {
     const int lane = lane_id(), N = p.N;
@@ -2524,28 +2537,58 @@ __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row
     ValidSink sink;
     sink.act = nullptr; sink.mask = nullptr; sink.cap = 0; sink.vm = vm;
     sink.have_sizes = 1; sink.w_lo = z.w_lo; sink.h_lo = z.h_lo; sink.w_hi = z.w_hi; sink.h_hi = z.h_hi;
+    int wt_lo = 1, wt_hi = 1;
+    if (WT) {
+        wt_lo = policy_weight(z.w_lo, z.h_lo, p.pol_w, p.pol_h);
+        if (big) wt_hi = policy_weight(z.w_hi, z.h_hi, p.pol_w, p.pol_h);
+    }
     int moves = 0;
     for (int s = 0; s < N; ++s) {
         const int nv = gen_valid_moves<row_t, BIG>(p, wh, myrow, rem0, rem1, sink);
         if (nv <= 0) break;
         const u64 m_lo = vm[lane], m_hi = big ? vm[64 + lane] : 0ull;
         lds_sync();  // the masks are in registers before the next gen_valid_moves clears the words
-        const int pick = (int)__umul64hi(sample_u64(h0, j, (u64)s), (u64)nv);  // 0 <= pick < nv
-        const int inc_lo = (int)wave_scan_add((u32)__popcll(m_lo));
-        const int tot_lo = __builtin_amdgcn_readlane(inc_lo, 63);
         int item, skip;  // the item that owns legal move `pick`, and how many of its columns come before it
         u64 own;
-        if (pick < tot_lo) {
-            const int l = __ffsll((long long)__ballot(pick < inc_lo)) - 1;  // first item whose inclusive count exceeds pick
-            item = l;
-            skip = pick - (__builtin_amdgcn_readlane(inc_lo, l) - __popcll(uni(__shfl(m_lo, l))));
-            own = uni(__shfl(m_lo, l));
+        if (WT) {
+            const int cw_lo = __popcll(m_lo) * wt_lo, cw_hi = big ? __popcll(m_hi) * wt_hi : 0;  // lanes without an item hold an empty mask
+            const int inc_lo = (int)wave_scan_add((u32)cw_lo);
+            const int tot_lo = __builtin_amdgcn_readlane(inc_lo, 63);
+            int inc_hi = 0, total = tot_lo;
+            if (big) { inc_hi = (int)wave_scan_add((u32)cw_hi); total += __builtin_amdgcn_readlane(inc_hi, 63); }
+            const int pick = (int)__umul64hi(sample_u64(h0, j, (u64)s), (u64)(u32)total);  // 0 <= pick < total
+            int unit, wt;  // the pick's offset among the owning item's units, and the item's weight
+            if (pick < tot_lo) {
+                const int l = __ffsll((long long)__ballot(pick < inc_lo)) - 1;  // first item whose inclusive sum exceeds pick
+                item = l;
+                unit = pick - (__builtin_amdgcn_readlane(inc_lo, l) - __builtin_amdgcn_readlane(cw_lo, l));
+                wt = __builtin_amdgcn_readlane(wt_lo, l);
+                own = uni(__shfl(m_lo, l));
+            } else {
+                const int q = pick - tot_lo;
+                const int l = __ffsll((long long)__ballot(q < inc_hi)) - 1;
+                item = 64 + l;
+                unit = q - (__builtin_amdgcn_readlane(inc_hi, l) - __builtin_amdgcn_readlane(cw_hi, l));
+                wt = __builtin_amdgcn_readlane(wt_hi, l);
+                own = uni(__shfl(m_hi, l));
+            }
+            skip = (int)((u32)unit / (u32)wt);  // wt >= 1: the owning item has a legal column, so its lane holds an item
         } else {
-            const int inc_hi = (int)wave_scan_add((u32)__popcll(m_hi)), q = pick - tot_lo;
-            const int l = __ffsll((long long)__ballot(q < inc_hi)) - 1;
-            item = 64 + l;
-            skip = q - (__builtin_amdgcn_readlane(inc_hi, l) - __popcll(uni(__shfl(m_hi, l))));
-            own = uni(__shfl(m_hi, l));
+            const int pick = (int)__umul64hi(sample_u64(h0, j, (u64)s), (u64)nv);  // 0 <= pick < nv
+            const int inc_lo = (int)wave_scan_add((u32)__popcll(m_lo));
+            const int tot_lo = __builtin_amdgcn_readlane(inc_lo, 63);
+            if (pick < tot_lo) {
+                const int l = __ffsll((long long)__ballot(pick < inc_lo)) - 1;  // first item whose inclusive count exceeds pick
+                item = l;
+                skip = pick - (__builtin_amdgcn_readlane(inc_lo, l) - __popcll(uni(__shfl(m_lo, l))));
+                own = uni(__shfl(m_lo, l));
+            } else {
+                const int inc_hi = (int)wave_scan_add((u32)__popcll(m_hi)), q = pick - tot_lo;
+                const int l = __ffsll((long long)__ballot(q < inc_hi)) - 1;
+                item = 64 + l;
+                skip = q - (__builtin_amdgcn_readlane(inc_hi, l) - __popcll(uni(__shfl(m_hi, l))));
+                own = uni(__shfl(m_hi, l));
+            }
         }
         for (int k = 0; k < skip; ++k) own &= own - 1;  // skip < popcount(own) <= 64
         const int col = __ffsll((long long)own) - 1;
@@ -2571,7 +2614,7 @@ __device__ int playout_outcome(const DP &p, row_t myrow, u64 rem0, u64 rem1, int
 // strictly greater -- so the same leaf offered twice changes nothing.  The winner is then played again from the leaf, a function of
 // (h0, j) alone, with the action sink pointed behind the head of the list (played moves, then the leaf's path as k_search stored it for
 // the commit), and its final state is the record's board and outcome.  One wave, all lanes; every lane holds the same r and j.
-template <typename row_t, bool BIG>
+template <typename row_t, bool BIG, bool WT>
 __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
     const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
     const int lane = lane_id();
@@ -2596,7 +2639,7 @@ __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
     const ItemSizes z = load_item_sizes<BIG>(t.wh, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ p.episode[g]);
     const int room = tree_moves < p.N ? p.N - tree_moves : 0;  // every move places one item: the list never outgrows N
-    const int m = random_playout<row_t, BIG, true>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, vm, rec.action() + (tree_moves < p.N ? tree_moves : 0), room);
+    const int m = random_playout<row_t, BIG, true, WT>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, vm, rec.action() + (tree_moves < p.N ? tree_moves : 0), room);
     double r_again;
     const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r_again);
     incumbent_lead(p, t, rec, prefix, depth, pe0, pn0, pe1, pn1);
@@ -2617,7 +2660,7 @@ __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
 // (playout_offer).  The host chooses the instantiation, one uniform branch per launch: as a run-time branch inside one kernel the offer
 // took k_rollout from 8 waves per SIMD to 7 and made it spill scalar registers with the mode off too (make resource-usage), so the
 // kernel of the mode that is off stays the code it was.
-template <typename row_t, bool BIG, bool TRACK>
+template <typename row_t, bool BIG, bool TRACK, bool WT>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int playouts, float *pi, float *v, long long capacity_rows) {
     const int b = blockIdx.x, wv = wave_in_block();
     if (b >= (p.rows_identity ? p.G : *p.eval_count) || b >= capacity_rows) return;
@@ -2639,7 +2682,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
     double best_r = 0.0;
     for (int j = wv; j < playouts; j += WAVES_PER_BLOCK) {
         row_t myrow = leaf; u64 rem0 = l0, rem1 = l1;
-        random_playout<row_t, BIG>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
+        random_playout<row_t, BIG, false, WT>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
         double r;
         sum += playout_outcome<row_t>(p, myrow, rem0, rem1, area, max_h, has_buf, bl, &r);
         if (TRACK && (best_j < 0 || r > best_r)) { best_r = r; best_j = j; }
@@ -2667,12 +2710,12 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
             const int jk = s_best_j[k];
             if (jk >= 0 && (rk > r || (rk == r && jk < j))) { r = rk; j = jk; }
         }
-        playout_offer<row_t, BIG>(p, g, r, uni(j), s_vm[0]);
+        playout_offer<row_t, BIG, WT>(p, g, r, uni(j), s_vm[0]);
     }
 }
 // The action lists of the playouts k_rollout_states plays, through the recording path of the playout offers: one wave per (state,
 // playout), zeros past the playout's moves.
-template <typename row_t, bool BIG>
+template <typename row_t, bool BIG, bool WT>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_paths(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh, const u64 *episode,
                                                                          u16 *action, int *moves_out) {
     const long long idx = (long long)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
@@ -2686,13 +2729,13 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_paths(DP p, lo
     const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
     u16 *mine = action + idx * p.N;
-    const int moves = random_playout<row_t, BIG, true>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()], mine, p.N);
+    const int moves = random_playout<row_t, BIG, true, WT>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()], mine, p.N);
     for (int q = lane; q < p.N; q += 64)
         if (q >= moves) mine[q] = (u16)0;
     if (lane == 0) moves_out[idx] = moves;
 }
 // The stateless batch form: one wave per (state, playout) of B host states, K playouts each.
-template <typename row_t, bool BIG>
+template <typename row_t, bool BIG, bool WT>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh,
                                                                           const int *area, const int *max_h, const u64 *episode, int has_buf, double bl,
                                                                           int *outcome, double *score, int *moves_out, u64 *board) {
@@ -2706,7 +2749,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, l
     const u8 *w2 = wh + b * p.N * 2;
     const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
-    const int moves = random_playout<row_t, BIG>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()]);
+    const int moves = random_playout<row_t, BIG, false, WT>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()]);
     double r;
     const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, area[b], max_h[b], has_buf != 0, bl, &r);
     if (lane == 0) { outcome[idx] = e; score[idx] = r; moves_out[idx] = moves; }
@@ -5179,6 +5222,9 @@ extern "C" int rp_game_ended(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
 }
 
 #define RP_MAX_PLAYOUTS 256
+// The rollout kernels come in a uniform and a weighted form (random_playout's WT): the host picks one per launch, so the uniform
+// kernels are the code they were before the policy existed.
+static bool weighted_playouts(const DP &d) { return d.pol_w != 0 || d.pol_h != 0; }
 
 extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, float *v_dev, int64_t capacity_rows) {
     if (!ctx || !v_dev || capacity_rows < 0) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: bad argument");
@@ -5186,11 +5232,11 @@ extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, flo
     const DP &d = ctx->d;
     long long rows = std::min<long long>(capacity_rows, d.G);
     if (rows == 0) return RP_OK;
-    if (d.inc_src)  // playout incumbents: the instantiation that also makes each leaf's offer
-        return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag, true>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev,
-                      v_dev, capacity_rows);
-    return launch(ctx, "k_rollout", GEO_KERNEL(ctx, d.N > 64, k_rollout<row_t, geo.flag, false>), dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev,
-                  v_dev, capacity_rows);
+    // playout incumbents: the instantiation that also makes each leaf's offer; a playout policy: the one that weighs the moves
+    const bool big = d.N > 64;
+    const auto fn = d.inc_src ? (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, false>))
+                              : (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, false>));
+    return launch(ctx, "k_rollout", fn, dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev, v_dev, capacity_rows);
 }
 
 extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
@@ -5220,9 +5266,8 @@ extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, c
     int *dmoves = s.out(moves_out, n);
     u64 *dboard = board_out ? s.out((u64 *)board_out, n * d.H) : nullptr;
     int rc = s.ok();
-    if (rc == RP_OK)
-        rc = launch_waves(ctx, "k_rollout_states", GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag>), (long long)n, d, B, playouts, drows, drem, dwh, darea, dmh,
-                          dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
+    const auto fn = weighted_playouts(d) ? GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag, true>) : GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag, false>);
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_states", fn, (long long)n, d, B, playouts, drows, drem, dwh, darea, dmh, dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
     return rc == RP_OK ? s.finish() : rc;
 }
 
@@ -5243,9 +5288,8 @@ extern "C" int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, co
     u16 *dact = s.out((u16 *)action_out, n * d.N);
     int *dmoves = s.out(moves_out, n);
     int rc = s.ok();
-    if (rc == RP_OK)
-        rc = launch_waves(ctx, "k_rollout_paths", GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag>), (long long)n, d, B, playouts, drows, drem, dwh, dep, dact,
-                          dmoves);
+    const auto fn = weighted_playouts(d) ? GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, true>) : GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, false>);
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_paths", fn, (long long)n, d, B, playouts, drows, drem, dwh, dep, dact, dmoves);
     return rc == RP_OK ? s.finish() : rc;
 }
 
@@ -5433,6 +5477,30 @@ extern "C" int rp_set_incumbent_playouts(rp_ctx *ctx, int32_t enable) {
         ctx->inc_src = src;
     }
     d.inc_src = enable ? ctx->inc_src : nullptr;
+    return RP_OK;
+}
+
+extern "C" int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_playout_policy: bad argument");
+    if (w_pow < 0 || h_pow < 0 || w_pow + h_pow > 2)
+        return fail(ctx, RP_ERR_ARG, "rp_set_playout_policy: powers (%d, %d) outside w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2", w_pow, h_pow);
+    DP &d = ctx->d;
+    {   // not while episodes are being played: an incumbent's record would stop being a function of the search alone
+        std::vector<int> ph((size_t)d.G);
+        HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int g = 0; g < d.G; ++g)
+            if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY)
+                return fail(ctx, RP_ERR_STATE, "rp_set_playout_policy: slot %d is in the middle of an episode; switch the policy between pools", g);
+    }
+    d.pol_w = w_pow; d.pol_h = h_pow;
+    return RP_OK;
+}
+
+extern "C" int rp_playout_policy(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out) {
+    if (!ctx) return RP_ERR_ARG;
+    if (w_pow_out) *w_pow_out = ctx->d.pol_w;
+    if (h_pow_out) *h_pow_out = ctx->d.pol_h;
     return RP_OK;
 }
 

@@ -12,6 +12,7 @@ own engine context, HIP stream and captured HIP graph of one simulation WAVE:
 
 With evaluator="rollout" the two middle steps are one kernel, rp_rollout_eval: every waiting leaf's value is the mean outcome of
 `playouts` uniform random playouts and its prior is uniform -- plain MCTS with no network, the baseline a trained net is compared with.
+playout_policy weighs a playout's legal moves by their item's size (rp_set_playout_policy); the default is uniform.
 
 The groups' waves are launched alternately on their streams, so the latency-bound tree walk of one group runs while the
 CNN of the other occupies the matrix cores.  Moves are played on device (`RP_MOVE_SAMPLE` / `RP_MOVE_ARGMAX_FIRST` / `_DRAW`) and a
@@ -45,6 +46,8 @@ class _Group:
             self.eng.set_incumbent(True)
         if owner.playout_incumbents:
             self.eng.set_incumbent_playouts(True)
+        if owner.playout_policy != (0, 0):
+            self.eng.set_playout_policy(*owner.playout_policy)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         self.wide_logits = owner.wide_logits
@@ -128,7 +131,7 @@ class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
                  tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False,
-                 playout_incumbents=False):
+                 playout_incumbents=False, playout_policy="uniform"):
         """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
         uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
         or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
@@ -143,6 +146,9 @@ class BatchedSelfPlay:
         playout_incumbents: with record_best and evaluator="rollout", every playout is a candidate too (rp_set_incumbent_playouts): each
         evaluated leaf offers its best playout, and an incumbent's `tree_moves` / `playout` say where it came from.  ValueError
         without record_best or with another evaluator.
+        playout_policy: with evaluator="rollout", how a playout chooses among the legal moves (rp_set_playout_policy): a name of
+        _lib.PLAYOUT_POLICIES or a pair (w_pow, h_pow) -- a move of an item (w, h) weighs w^w_pow * h^h_pow.  "uniform" (the default)
+        is (0, 0).  ValueError for anything else, and for a non-uniform policy with another evaluator.
         host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
         eagerly with one host round trip each.  tie_salt: salt of the deterministic `r == bl` tie (default: derived from seed)."""
@@ -176,6 +182,9 @@ class BatchedSelfPlay:
         self.playout_incumbents = bool(playout_incumbents)  # likewise
         if self.playout_incumbents and not (self.record_best and rollout):
             raise ValueError("playout_incumbents needs record_best=True and evaluator='rollout'")
+        self.playout_policy = _lib.playout_policy_powers(playout_policy)  # likewise
+        if self.playout_policy != (0, 0) and not rollout:
+            raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
         self._packings = []
         self._best = []
         self._pool_items = None

@@ -304,8 +304,13 @@ def play_packings(sp, item_wh=None, seeds=None, total_area=None, bin_h=None, bin
     return out
 
 
+def _evaluator_of(driver, driver_kw):
+    """The evaluator pack() will search with: the driver's, or the one its driver will be built with."""
+    return driver.evaluator if driver is not None else driver_kw.get("evaluator", "cnn")
+
+
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
-         driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, **driver_kw):
+         driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, playout_policy="uniform", **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
@@ -331,9 +336,16 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     is on.  A driver passed in must have been built with record_best=True.
     playout_incumbents (with best and evaluator="rollout"): every random playout the search runs is a candidate too
     (rp_set_incumbent_playouts) -- in a network-free search they are nearly all the finished packings it ever computes; the incumbents
-    then carry `tree_moves` and `playout`.  A driver passed in must have been built with the same setting."""
+    then carry `tree_moves` and `playout`.  A driver passed in must have been built with the same setting.
+    playout_policy (with evaluator="rollout"): how the playouts choose among the legal moves (rp_set_playout_policy) -- "uniform" (the
+    default), "area", "width", "width2", "height", "height2", or a pair (w_pow, h_pow): a move of an item (w, h) weighs
+    w^w_pow * h^h_pow.  ValueError for anything else and with the network as evaluator.  A driver passed in must have been built
+    with the same policy."""
     from .selfplay import BatchedSelfPlay
     _check_instances(item_wh, seeds, initial_board, remaining)
+    policy = _lib.playout_policy_powers(playout_policy)
+    if policy != (0, 0) and (_evaluator_of(driver, driver_kw) != "rollout"):
+        raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
@@ -343,9 +355,11 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
         sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
-                             playout_incumbents=bool(playout_incumbents), **driver_kw)
+                             playout_incumbents=bool(playout_incumbents), playout_policy=policy, **driver_kw)
     elif sp.playout_incumbents != bool(playout_incumbents):
         raise RuntimeError("the driver was built with playout_incumbents=%r" % sp.playout_incumbents)
+    elif sp.playout_policy != policy:
+        raise RuntimeError("the driver was built with playout_policy=%r" % (sp.playout_policy,))
     elif sp.move_rule != rule:
         sp.set_move_rule(rule)
     try:
@@ -356,19 +370,24 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
             sp.close()
 
 
-def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None, initial_board=None, remaining=None):
-    """Scores of uniform random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin, or
+def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None, initial_board=None, remaining=None,
+                  playout_policy="uniform"):
+    """Scores of random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin, or
     from (initial_board, remaining) as pack() takes them
     (rp_rollout_states; instance i plays as episode i, playout j draws from (seed, i, j)).  The random baseline a search or a trained
     network is compared with, and -- flattened -- a first R2 buffer for pack(..., evaluator="rollout", rewards_list=...).
-    item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them."""
+    item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them.  playout_policy: uniform over the legal moves by default, or
+    weighted by the item as pack() takes it -- a buffer for a search under a policy wants the scores of that policy."""
     _check_instances(item_wh, seeds, initial_board, remaining)
+    policy = _lib.playout_policy_powers(playout_policy)
     W, H, N = game.bin_width, game.bin_height, game.num_items
     rows0 = rem0 = None
     if seeds is None:  # checked before an engine is built
         item_wh, rows0, rem0, area = initial_state(W, H, N, item_wh, initial_board, remaining)
     eng = _lib.Engine(W, H, N, 1, 1, seed=int(seed) & 0x7FFFFFFFFFFFFFFF)
     try:
+        if policy != (0, 0):
+            eng.set_playout_policy(*policy)
         if seeds is not None:
             item_wh = eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
             area = np.full(len(item_wh), int(bin_w or W) * int(bin_h or H), np.int32)
