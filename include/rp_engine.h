@@ -40,8 +40,9 @@ extern "C" {
                              8: random-playout leaf evaluator (rp_rollout_eval, rp_rollout_states)
                              9: initial states of pool instances (rp_set_instance_initial)
                              10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents); additive, same number: playout
-                                 incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths) and the
-                                 playout policy (rp_set_playout_policy, rp_playout_policy) */
+                                 incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths), the
+                                 playout policy (rp_set_playout_policy, rp_playout_policy) and the rollout prior (rp_set_rollout_prior,
+                                 rp_rollout_prior, rp_rollout_prior_states) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -342,7 +343,8 @@ int rp_commit_eval_host(rp_ctx *ctx, const float *pi_host, const float *v_host, 
 /* MCTS_bpp.py:87 for the leaves waiting for evaluation: v_dev[b] = float32(sum of the `playouts` outcomes) / float32(playouts), row b as
  * in rp_leaf_planes, and -- when pi_dev != NULL -- pi_dev row b = float32(1) / float32(W * N) in every entry (the uniform prior;
  * rp_commit_eval masks and renormalises it).  DEVICE float32 buffers of capacity_rows rows.  Enqueues one kernel only: capturable.
- * 1 <= playouts <= 256, else RP_ERR_ARG. */
+ * 1 <= playouts <= 256, else RP_ERR_ARG.  Under a rollout prior other than (0, 0, 0) the rows of pi_dev are the prior's and one more
+ * kernel is enqueued (rp_set_rollout_prior below). */
 int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev /* may be NULL */, float *v_dev, int64_t capacity_rows);
 /* The same playouts (MCTS_bpp.py:87) over a batch of B host states, `playouts` each, with everything they produce: the resolved outcome
  * (+-1), the score r, the moves played (0 for a state without a legal move) and the final bin's row masks (board_out may be NULL).
@@ -382,6 +384,34 @@ int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t
 int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow);
 /* The powers in force (either pointer may be NULL). */
 int rp_playout_policy(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out);
+/* The rollout prior of the context: the pi that rp_rollout_eval returns in place of nnet.predict's (MCTS_bpp.py:87).  Three small
+ * integer powers (w_pow, h_pow, land_pow).  The default (0, 0, 0) is the uniform prior above.  The rule:
+ *   - For a leaf state, m_i is the legal-column mask of item i (getValidMoves, BinPackingGame.py:78-92).
+ *   - A legal move (i, c) gets the integer weight u(i, c) = w_i^w_pow * h_i^h_pow * (H - t(i, c))^land_pow.
+ *   - t(i, c) is the first row r, counted from 0, whose window [c, c + w_i) is empty: the t of get_adjacency
+ *     (BinPackingLogic.py:66-68), and, where an empty row exists, the row execute_move fills first (BinPackingLogic.py:103-105).
+ *     If no row of the window is empty, t = H - 1: the reference's `for` falls through.  Such moves exist, legality only counts cells
+ *     (BinPackingLogic.py:89).  So 1 <= H - t <= H: a move that lands low weighs more.
+ *   - Limits: w_pow, h_pow, land_pow >= 0, w_pow + h_pow <= 2, land_pow <= 2.  Then 1 <= u <= 4096 * 4096 = 2^24, which float32
+ *     holds exactly, and T = sum of u over all legal moves <= 8192 * 2^24 = 2^37: a 64-bit integer sum, whose value does not depend
+ *     on the summation order.
+ *   - pi[a] = float32(float64(u) / float64(T)) at the legal actions a = i * W + c -- one IEEE double division, rounded once to
+ *     float32 -- and 0.0f everywhere else.  A state without a legal move gives an all-zero row.
+ *   - With (0, 0, 0) the row is float32(1) / float32(W * N) in every entry, bit for bit what it was before the prior existed.
+ * rp_commit_eval masks and renormalises the row as it does any pi (MCTS_bpp.py:88-100); the row is non-negative, so the candidate
+ * rule for more than 64 legal moves (rp_commit_eval above) keeps holding.
+ * RP_ERR_ARG outside the limits; RP_ERR_STATE while any slot is in the middle of an episode (a search stays a function of one setting).
+ * From then on, while the prior is not (0, 0, 0): rp_rollout_eval writes pi_dev row b = the row above of the b-th waiting leaf, the row
+ * mapping of v_dev (compact rows included); pi_dev == NULL is RP_ERR_ARG, the prior has no other way out; the call enqueues two
+ * kernels and stays capturable.  Under (0, 0, 0) nothing about rp_rollout_eval changes.  Kernel arguments are baked into captured
+ * graphs: re-capture after switching. */
+int rp_set_rollout_prior(rp_ctx *ctx, int32_t w_pow, int32_t h_pow, int32_t land_pow);
+/* The powers in force (any pointer may be NULL). */
+int rp_rollout_prior(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out, int32_t *land_pow_out);
+/* The prior rows of a batch of B host states under the prior in force, stateless like rp_rollout_states: pi_out row b is the row
+ * above for state b (float32(1) / float32(W * N) in every entry under (0, 0, 0)). */
+int rp_rollout_prior_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh,
+                            float *pi_out /* HOST [B][W*N] */);
 
 /* ---- results ------------------------------------------------------------------------- */
 /* counts[a] = Nsa[(root, a)] (MCTS_bpp.py:40-41), host buffer [count][W*N] */

@@ -69,6 +69,9 @@ _SIGS = {
     "rp_incumbent_sources": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_set_playout_policy": (C.c_int, [_vp, _i32, _i32]),
     "rp_playout_policy": (C.c_int, [_vp, _vp, _vp]),
+    "rp_set_rollout_prior": (C.c_int, [_vp, _i32, _i32, _i32]),
+    "rp_rollout_prior": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "rp_rollout_prior_states": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "rp_last_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_search_step": (C.c_int, [_vp, _vp]),
     "rp_leaf_planes": (C.c_int, [_vp, _vp, _i64]),
@@ -141,6 +144,29 @@ def playout_policy_powers(policy):
     if not ok or w_pow < 0 or h_pow < 0 or w_pow + h_pow > 2:
         raise ValueError("playout policy %r: a name or a pair of integers (w_pow, h_pow), w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2" % (policy,))
     return int(w_pow), int(h_pow)
+
+# names of the rollout priors (rp_set_rollout_prior): the powers (w_pow, h_pow, land_pow) of a legal move's weight
+# w^w_pow * h^h_pow * (H - t)^land_pow, t = the first row whose window under the item is empty
+ROLLOUT_PRIORS = {"uniform": (0, 0, 0), "low": (0, 0, 1), "low2": (0, 0, 2), "width2": (2, 0, 0), "area": (1, 1, 0), "width2-low2": (2, 0, 2)}
+
+
+def rollout_prior_powers(prior):
+    """A rollout prior as its triple of powers: one of ROLLOUT_PRIORS' names, or a triple of integers (w_pow, h_pow, land_pow), all
+    >= 0, with w_pow + h_pow <= 2 and land_pow <= 2; None is uniform.  ValueError for anything else."""
+    if prior is None:
+        return 0, 0, 0
+    if isinstance(prior, str):
+        if prior not in ROLLOUT_PRIORS:
+            raise ValueError("unknown rollout prior %r: one of %s, or a triple (w_pow, h_pow, land_pow)" % (prior, ", ".join(sorted(ROLLOUT_PRIORS))))
+        return ROLLOUT_PRIORS[prior]
+    try:
+        w_pow, h_pow, land_pow = prior
+        ok = all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (w_pow, h_pow, land_pow))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or w_pow < 0 or h_pow < 0 or land_pow < 0 or w_pow + h_pow > 2 or land_pow > 2:
+        raise ValueError("rollout prior %r: a name or a triple of integers (w_pow, h_pow, land_pow), all >= 0, w_pow + h_pow <= 2, land_pow <= 2" % (prior,))
+    return int(w_pow), int(h_pow), int(land_pow)
 
 
 def load():
@@ -370,6 +396,27 @@ class Engine:
         w, h = _i32(0), _i32(0)
         self._ck(self.L.rp_playout_policy(self.h, C.byref(w), C.byref(h)))
         return int(w.value), int(h.value)
+
+    def set_rollout_prior(self, w_pow, h_pow, land_pow):
+        """Rollout prior (rp_set_rollout_prior): rollout_eval's pi rows weigh a legal move (i, c) by w_i^w_pow * h_i^h_pow *
+        (H - t)^land_pow, t the first row whose window under the item is empty; (0, 0, 0) is uniform.  Refused outside the limits and
+        while a slot is in mid-episode; rollout_eval then needs pi_ptr; re-capture graphs after switching."""
+        self._ck(self.L.rp_set_rollout_prior(self.h, int(w_pow), int(h_pow), int(land_pow)))
+
+    def rollout_prior(self):
+        """The powers (w_pow, h_pow, land_pow) in force (rp_rollout_prior)."""
+        w, h, t = _i32(0), _i32(0), _i32(0)
+        self._ck(self.L.rp_rollout_prior(self.h, C.byref(w), C.byref(h), C.byref(t)))
+        return int(w.value), int(h.value), int(t.value)
+
+    def rollout_prior_states(self, rows, remaining, item_wh):
+        """The prior rows of B host states under the prior in force (rp_rollout_prior_states) -> float32 [B, A]."""
+        rows = _arr(rows, np.uint64); B = rows.shape[0]
+        rows = _arr(rows, np.uint64, (B, self.H)); remaining = _arr(remaining, np.uint8, (B, self.N))
+        item_wh = _arr(item_wh, np.uint8, (B, self.N, 2))
+        pi = np.zeros((B, self.A), np.float32)
+        self._ck(self.L.rp_rollout_prior_states(self.h, B, _ptr(rows), _ptr(remaining), _ptr(item_wh), _ptr(pi)))
+        return pi
 
     def incumbent_sources(self, first=0, count=None):
         """Where the running incumbents came from (rp_incumbent_sources) -> dict of tree_moves / playout i32 [n]: the actions after which
@@ -616,8 +663,8 @@ class Engine:
 
     def rollout_eval(self, v_ptr, capacity_rows, playouts, pi_ptr=None):
         """Random-playout evaluator of the waiting leaves (rp_rollout_eval): v[b] = mean outcome of `playouts` random playouts -- uniform
-        over the legal moves, or weighted by the item under set_playout_policy -- and, with pi_ptr, pi row b = 1 / A.  Device pointers of
-        capacity_rows rows; enqueues only."""
+        over the legal moves, or weighted by the item under set_playout_policy -- and, with pi_ptr, pi row b = 1 / A, or the leaf's
+        prior row under set_rollout_prior (pi_ptr is then required).  Device pointers of capacity_rows rows; enqueues only."""
         self._ck(self.L.rp_rollout_eval(self.h, int(playouts), C.c_void_p(pi_ptr) if pi_ptr else None, C.c_void_p(v_ptr), int(capacity_rows)))
 
     def rollout_states(self, rows, remaining, item_wh, total_area, max_h, rewards, alpha, playouts, episode_id=None, boards=True):

@@ -2756,6 +2756,109 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, l
     if (board && lane < p.H) board[idx * p.H + lane] = (u64)myrow;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Heuristic prior of the network-free search (rp_set_rollout_prior): three powers (w_pow, h_pow, land_pow), not all 0.  A legal move
+// (i, c) weighs u(i, c) = w_i^w_pow * h_i^h_pow * (H - t(i, c))^land_pow, t = the first row whose window [c, c + w_i) is empty, H - 1
+// if none is (get_adjacency's t, BinPackingLogic.py:66-68).  1 <= u <= 2^24, T = sum of u <= 8192 * 2^24 = 2^37: a 64-bit integer
+// sum, whatever its order.  pi[a] = float32(float64(u) / float64(T)) at the legal actions, 0.0f elsewhere; all zero without a legal move.
+// One wave per leaf, lane r = row r.  gen_valid_moves leaves the legal-column masks m_i in the wave's LDS words.  Then, per width w
+// that an unplaced item has, F = E_w & ~Xex as in gen_valid_moves -- bit c of lane r: row r is the first empty row of window
+// [c, c + w), the fall-through on lane H - 1 -- and for every column c that some item of the width may take, the one set lane of
+// ballot(bit c of F) is t(w, c), kept by lane c.  Lanes = columns from there: lane c adds the weights of its column's legal moves in
+// 64 bits and stores each u, exact in float32, into the zero-filled row; a wave reduction gives T and a second pass over the row
+// divides.  Two passes over a row that stays in L2 instead of the t of every (width, column) in LDS.  A kernel of its own beside
+// k_rollout: the host launches it only under a non-uniform prior, so the kernels of the uniform prior are the code they were.  F is
+// formed a second time here rather than taken from a sink inside gen_valid_moves: that function is k_search's too, which has neither
+// a vector nor a scalar register to spare (make resource-usage), and the prior pays for it once per leaf, not per playout step.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+struct Prior { int w_pow, h_pow, land_pow; };
+template <typename row_t, bool BIG>
+__device__ void prior_row(const DP &p, const u8 *wh, row_t myrow, u64 rem0, u64 rem1, u64 *vm, float *row, Prior pr) {
+    const int lane = lane_id(), W = p.W, H = p.H, N = p.N;
+    const bool big = BIG && N > 64;
+    const ItemSizes z = load_item_sizes<BIG>(wh, N);
+    ValidSink sink;
+    sink.act = nullptr; sink.mask = nullptr; sink.cap = 0; sink.vm = vm;
+    sink.have_sizes = 1; sink.w_lo = z.w_lo; sink.h_lo = z.h_lo; sink.w_hi = z.w_hi; sink.h_hi = z.h_hi;
+    const int nv = gen_valid_moves<row_t, BIG>(p, wh, myrow, rem0, rem1, sink);
+    for (int a = lane; a < p.A; a += 64) row[a] = 0.0f;
+    if (nv <= 0) return;
+    wave_sync();  // the zeros are behind the weights other lanes store to the same words below
+    const int iw_lo = policy_weight(z.w_lo, z.h_lo, pr.w_pow, pr.h_pow), iw_hi = big ? policy_weight(z.w_hi, z.h_hi, pr.w_pow, pr.h_pow) : 0;
+    const bool un_lo = lane < N && ((rem0 >> lane) & 1ull), un_hi = big && lane + 64 < N && ((rem1 >> lane) & 1ull);
+    const row_t full = (row_t)full_mask(W);
+    const row_t E1 = lane < H ? (row_t)(~myrow & full) : (row_t)0;
+    row_t E = E1;
+    u64 sum = 0;  // lane c: the weights of the legal moves into column c
+    for (int w = 1; w <= W; ++w) {
+        if (w > 1) E = E & (row_t)(E1 >> (w - 1));
+        const u64 im0 = __ballot(un_lo && z.w_lo == w), im1 = big ? __ballot(un_hi && z.w_hi == w) : 0ull;
+        u64 cols = 0ull;  // columns some item of this width may legally take
+        for (u64 m = im0; m; m &= m - 1) cols |= vm[__ffsll((long long)m) - 1];
+        for (u64 m = im1; m; m &= m - 1) cols |= vm[64 + __ffsll((long long)m) - 1];
+        cols = uni(cols);
+        if (cols == 0ull) continue;
+        const row_t X = wave_scan_or(E);
+        const row_t Xex = wave_shift_up1(X);
+        const row_t anyrow = RowOps<row_t>::at(X, 63);
+        row_t F = (row_t)(E & ~Xex);                                 // this row is the first empty one of the window
+        if (lane == H - 1) F |= (row_t)(~anyrow & full);            // none is: t = H - 1 (:66-68)
+        int t = 0;
+        for (u64 m = cols; m; m &= m - 1) {
+            const int c = __ffsll((long long)m) - 1;
+            const int tc = __ffsll((long long)__ballot(((F >> c) & (row_t)1) != 0)) - 1;
+            if (lane == c) t = tc;
+        }
+        const int land = policy_power(H - t, pr.land_pow);
+        for (u64 m = im0; m; m &= m - 1) {
+            const int i = __ffsll((long long)m) - 1;
+            const u64 mi = vm[i];
+            const u32 u = (u32)__builtin_amdgcn_readlane(iw_lo, i) * (u32)land;
+            if ((mi >> lane) & 1ull) { sum += u; row[i * W + lane] = (float)u; }
+        }
+        for (u64 m = im1; m; m &= m - 1) {
+            const int i = __ffsll((long long)m) - 1;
+            const u64 mi = vm[64 + i];
+            const u32 u = (u32)__builtin_amdgcn_readlane(iw_hi, i) * (u32)land;
+            if ((mi >> lane) & 1ull) { sum += u; row[(64 + i) * W + lane] = (float)u; }
+        }
+    }
+    const double T = (double)uni(wave_sum_u64(sum));  // <= 2^37: exact
+    wave_sync();
+    for (int a = lane; a < p.A; a += 64) {
+        const float u = row[a];
+        if (u != 0.0f) row[a] = (float)((double)u / T);  // one IEEE division, rounded once to float32
+    }
+}
+// The waiting leaves, in k_rollout's row mapping: one wave per evaluator row.
+template <typename row_t, bool BIG>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_prior(DP p, float *pi, long long capacity_rows, Prior pr) {
+    const int b = blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
+    if (b >= (p.rows_identity ? p.G : *p.eval_count) || b >= capacity_rows) return;
+    const int g = __builtin_amdgcn_readfirstlane(p.rows_identity ? b : p.eval_slot[b]);
+    if (p.phase[g] != RP_PHASE_WAIT_EVAL) return;
+    __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
+    Tree<row_t, BIG> t(p, g);
+    row_t leaf; u64 l0, l1;
+    t.load_key(p.leaf_node[g], leaf, l0, l1);
+    prior_row<row_t, BIG>(p, t.wh, leaf, l0, l1, s_vm[wave_in_block()], pi + (size_t)b * p.A, pr);
+}
+// The stateless batch form: one wave per host state.
+template <typename row_t, bool BIG>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_prior_states(DP p, long long B, const u64 *rows, const u8 *rem, const u8 *wh, float *pi, Prior pr) {
+    const long long b = (long long)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
+    if (b >= B) return;
+    __shared__ u64 s_vm[WAVES_PER_BLOCK][VM_WORDS];
+    row_t myrow; u64 rem0, rem1;
+    load_host_state<row_t>(p, rows + b * p.H, rem + b * p.N, myrow, rem0, rem1);
+    prior_row<row_t, BIG>(p, wh + b * p.N * 2, myrow, rem0, rem1, s_vm[wave_in_block()], pi + (size_t)b * p.A, pr);
+}
+
 __global__ void k_fill_rank(DP p, double bl, int has_buf) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g < p.G) { p.bl[g] = bl; p.has_buf[g] = has_buf; }
@@ -4501,6 +4604,9 @@ struct rp_ctx {
     u8 *inc = nullptr, *fin_inc = nullptr;
     IncNew *inc_new = nullptr;
     int *inc_src = nullptr;  // rp_set_incumbent_playouts
+    // rp_set_rollout_prior: the powers of the heuristic prior.  All 0 = uniform: rp_rollout_eval then launches what it launched before the
+    // prior existed.  Host state, handed to k_rollout_prior as an argument: the device view and every other kernel's arguments stay as they are.
+    Prior prior = {0, 0, 0};
 };
 
 static std::string g_create_error;
@@ -5225,15 +5331,22 @@ extern "C" int rp_game_ended(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
 // The rollout kernels come in a uniform and a weighted form (random_playout's WT): the host picks one per launch, so the uniform
 // kernels are the code they were before the policy existed.
 static bool weighted_playouts(const DP &d) { return d.pol_w != 0 || d.pol_h != 0; }
+static bool heuristic_prior(const rp_ctx *ctx) { return ctx->prior.w_pow != 0 || ctx->prior.h_pow != 0 || ctx->prior.land_pow != 0; }
 
 extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, float *v_dev, int64_t capacity_rows) {
     if (!ctx || !v_dev || capacity_rows < 0) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: bad argument");
     if (playouts < 1 || playouts > RP_MAX_PLAYOUTS) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: playouts %d outside 1..%d", playouts, RP_MAX_PLAYOUTS);
     const DP &d = ctx->d;
     long long rows = std::min<long long>(capacity_rows, d.G);
+    if (heuristic_prior(ctx) && !pi_dev) return fail(ctx, RP_ERR_ARG, "rp_rollout_eval: the rollout prior in force needs pi_dev");
     if (rows == 0) return RP_OK;
     // playout incumbents: the instantiation that also makes each leaf's offer; a playout policy: the one that weighs the moves
     const bool big = d.N > 64;
+    if (heuristic_prior(ctx)) {  // the prior's rows come from a kernel of their own; k_rollout then writes v alone
+        const int rc = launch_waves(ctx, "k_rollout_prior", GEO_KERNEL(ctx, big, k_rollout_prior<row_t, geo.flag>), rows, d, pi_dev, capacity_rows, ctx->prior);
+        if (rc != RP_OK) return rc;
+        pi_dev = nullptr;
+    }
     const auto fn = d.inc_src ? (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, false>))
                               : (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, false>));
     return launch(ctx, "k_rollout", fn, dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev, v_dev, capacity_rows);
@@ -5290,6 +5403,26 @@ extern "C" int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, co
     int rc = s.ok();
     const auto fn = weighted_playouts(d) ? GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, true>) : GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, false>);
     if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_paths", fn, (long long)n, d, B, playouts, drows, drem, dwh, dep, dact, dmoves);
+    return rc == RP_OK ? s.finish() : rc;
+}
+
+extern "C" int rp_rollout_prior_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t *remaining, const uint8_t *item_wh, float *pi_out) {
+    if (!ctx || B < 0 || !rows || !remaining || !item_wh || !pi_out) return fail(ctx, RP_ERR_ARG, "rp_rollout_prior_states: bad argument");
+    if (B == 0) return RP_OK;
+    const DP &d = ctx->d;
+    if ((size_t)B > (size_t)0x7FFFFFFF) return fail(ctx, RP_ERR_ARG, "rp_rollout_prior_states: %lld states exceed 2^31 - 1", (long long)B);
+    if (item_sizes(ctx, "rp_rollout_prior_states", B, item_wh, nullptr, nullptr) != RP_OK) return RP_ERR_ARG;
+    if (!heuristic_prior(ctx)) {  // the uniform prior is a constant: k_rollout's 1 / A
+        std::fill(pi_out, pi_out + (size_t)B * d.A, 1.0f / (float)d.A);
+        return RP_OK;
+    }
+    Scratch s(ctx);
+    u64 *drows = s.in((const u64 *)rows, (size_t)B * d.H);
+    u8 *drem = s.in(remaining, (size_t)B * d.N);
+    u8 *dwh = s.in(item_wh, (size_t)B * d.N * 2);
+    float *dpi = s.out(pi_out, (size_t)B * d.A);
+    int rc = s.ok();
+    if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_prior_states", GEO_KERNEL(ctx, d.N > 64, k_rollout_prior_states<row_t, geo.flag>), B, d, B, drows, drem, dwh, dpi, ctx->prior);
     return rc == RP_OK ? s.finish() : rc;
 }
 
@@ -5480,20 +5613,51 @@ extern "C" int rp_set_incumbent_playouts(rp_ctx *ctx, int32_t enable) {
     return RP_OK;
 }
 
+// The first slot that is in the middle of an episode, -1 if none is (waits for the stream).
+static int slot_in_episode(rp_ctx *ctx, int *slot) {
+    const DP &d = ctx->d;
+    std::vector<int> ph((size_t)d.G);
+    HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *slot = -1;
+    for (int g = 0; g < d.G; ++g)
+        if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY) { *slot = g; break; }
+    return RP_OK;
+}
+
 extern "C" int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow) {
     if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_playout_policy: bad argument");
     if (w_pow < 0 || h_pow < 0 || w_pow + h_pow > 2)
         return fail(ctx, RP_ERR_ARG, "rp_set_playout_policy: powers (%d, %d) outside w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2", w_pow, h_pow);
     DP &d = ctx->d;
-    {   // not while episodes are being played: an incumbent's record would stop being a function of the search alone
-        std::vector<int> ph((size_t)d.G);
-        HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        for (int g = 0; g < d.G; ++g)
-            if (ph[g] == RP_PHASE_RUNNING || ph[g] == RP_PHASE_WAIT_EVAL || ph[g] == RP_PHASE_MOVE_READY)
-                return fail(ctx, RP_ERR_STATE, "rp_set_playout_policy: slot %d is in the middle of an episode; switch the policy between pools", g);
-    }
+    // not while episodes are being played: an incumbent's record would stop being a function of the search alone
+    int g = -1;
+    const int rc = slot_in_episode(ctx, &g);
+    if (rc != RP_OK) return rc;
+    if (g >= 0) return fail(ctx, RP_ERR_STATE, "rp_set_playout_policy: slot %d is in the middle of an episode; switch the policy between pools", g);
     d.pol_w = w_pow; d.pol_h = h_pow;
+    return RP_OK;
+}
+
+extern "C" int rp_set_rollout_prior(rp_ctx *ctx, int32_t w_pow, int32_t h_pow, int32_t land_pow) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_rollout_prior: bad argument");
+    if (w_pow < 0 || h_pow < 0 || land_pow < 0 || w_pow + h_pow > 2 || land_pow > 2)
+        return fail(ctx, RP_ERR_ARG, "rp_set_rollout_prior: powers (%d, %d, %d) outside w_pow, h_pow, land_pow >= 0, w_pow + h_pow <= 2, land_pow <= 2", w_pow, h_pow,
+                    land_pow);
+    // not while episodes are being played: a search stays a function of one setting
+    int g = -1;
+    const int rc = slot_in_episode(ctx, &g);
+    if (rc != RP_OK) return rc;
+    if (g >= 0) return fail(ctx, RP_ERR_STATE, "rp_set_rollout_prior: slot %d is in the middle of an episode; switch the prior between pools", g);
+    ctx->prior = Prior{w_pow, h_pow, land_pow};
+    return RP_OK;
+}
+
+extern "C" int rp_rollout_prior(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out, int32_t *land_pow_out) {
+    if (!ctx) return RP_ERR_ARG;
+    if (w_pow_out) *w_pow_out = ctx->prior.w_pow;
+    if (h_pow_out) *h_pow_out = ctx->prior.h_pow;
+    if (land_pow_out) *land_pow_out = ctx->prior.land_pow;
     return RP_OK;
 }
 

@@ -13,6 +13,8 @@ own engine context, HIP stream and captured HIP graph of one simulation WAVE:
 With evaluator="rollout" the two middle steps are one kernel, rp_rollout_eval: every waiting leaf's value is the mean outcome of
 `playouts` uniform random playouts and its prior is uniform -- plain MCTS with no network, the baseline a trained net is compared with.
 playout_policy weighs a playout's legal moves by their item's size (rp_set_playout_policy); the default is uniform.
+rollout_prior replaces the uniform prior by one that weighs a legal move by its item's size and the row it lands on
+(rp_set_rollout_prior); the default is uniform.
 
 The groups' waves are launched alternately on their streams, so the latency-bound tree walk of one group runs while the
 CNN of the other occupies the matrix cores.  Moves are played on device (`RP_MOVE_SAMPLE` / `RP_MOVE_ARGMAX_FIRST` / `_DRAW`) and a
@@ -48,6 +50,9 @@ class _Group:
             self.eng.set_incumbent_playouts(True)
         if owner.playout_policy != (0, 0):
             self.eng.set_playout_policy(*owner.playout_policy)
+        self.prior = owner.rollout_prior != (0, 0, 0)
+        if self.prior:
+            self.eng.set_rollout_prior(*owner.rollout_prior)
         self.use_stem = owner.use_stem
         self.host_evaluator = owner.host_evaluator
         self.wide_logits = owner.wide_logits
@@ -56,6 +61,8 @@ class _Group:
         if self.rollout:  # no network: the uniform prior is written once, the playout kernel fills v every wave
             self.planes = None
             self.uniform_pi = torch.full((games, owner.A), float(np.float32(1) / np.float32(owner.A)), dtype=torch.float32, device=owner.device)
+            # a rollout prior: the group's own rows, written by rollout_eval every wave
+            self.prior_pi = torch.zeros((games, owner.A), dtype=torch.float32, device=owner.device) if self.prior else None
             self.rollout_v = torch.zeros(games, dtype=torch.float32, device=owner.device)
         elif self.use_stem:  # the engine computes the first conv + pool itself: no plane tensor at all
             self.channels_last = owner.channels_last
@@ -119,6 +126,10 @@ class _Group:
             return
         self.eng.search_step(sync=False)
         if self.rollout:
+            if self.prior:
+                self.eng.rollout_eval(self.rollout_v.data_ptr(), self.G, self.playouts, pi_ptr=self.prior_pi.data_ptr())
+                self.eng.commit_eval(self.prior_pi.data_ptr(), self.rollout_v.data_ptr())
+                return
             self.eng.rollout_eval(self.rollout_v.data_ptr(), self.G, self.playouts)
             self.eng.commit_eval(self.uniform_pi.data_ptr(), self.rollout_v.data_ptr())
             return
@@ -131,7 +142,7 @@ class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
                  tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False,
-                 playout_incumbents=False, playout_policy="uniform"):
+                 playout_incumbents=False, playout_policy="uniform", rollout_prior="uniform"):
         """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
         uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
         or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
@@ -149,6 +160,9 @@ class BatchedSelfPlay:
         playout_policy: with evaluator="rollout", how a playout chooses among the legal moves (rp_set_playout_policy): a name of
         _lib.PLAYOUT_POLICIES or a pair (w_pow, h_pow) -- a move of an item (w, h) weighs w^w_pow * h^h_pow.  "uniform" (the default)
         is (0, 0).  ValueError for anything else, and for a non-uniform policy with another evaluator.
+        rollout_prior: with evaluator="rollout", the prior of a leaf (rp_set_rollout_prior): a name of _lib.ROLLOUT_PRIORS or a triple
+        (w_pow, h_pow, land_pow) -- a legal move of an item (w, h) that lands on row t weighs w^w_pow * h^h_pow * (H - t)^land_pow.
+        "uniform" (the default) is (0, 0, 0).  ValueError for anything else, and for a non-uniform prior with another evaluator.
         host_evaluator: optional callable (rows [n][H] uint64, remaining [n][N] uint8, slots [n]) -> (pi [n][A] float32, v [n]
         float32) that replaces the CNN -- any object with the reference's `predict` contract can sit behind it; the waves then run
         eagerly with one host round trip each.  tie_salt: salt of the deterministic `r == bl` tie (default: derived from seed)."""
@@ -185,6 +199,9 @@ class BatchedSelfPlay:
         self.playout_policy = _lib.playout_policy_powers(playout_policy)  # likewise
         if self.playout_policy != (0, 0) and not rollout:
             raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
+        self.rollout_prior = _lib.rollout_prior_powers(rollout_prior)  # likewise
+        if self.rollout_prior != (0, 0, 0) and not rollout:
+            raise ValueError("a rollout prior other than 'uniform' needs evaluator='rollout'")
         self._packings = []
         self._best = []
         self._pool_items = None
@@ -214,7 +231,7 @@ class BatchedSelfPlay:
     def close(self):
         for g in self.groups:
             g.graph = None
-            g.pi = g.v = g.stem = g.stem_relu = g.planes = g.uniform_pi = g.rollout_v = None
+            g.pi = g.v = g.stem = g.stem_relu = g.planes = g.uniform_pi = g.prior_pi = g.rollout_v = None
             g.eng.close()
 
     @property

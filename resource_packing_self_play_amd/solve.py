@@ -310,7 +310,8 @@ def _evaluator_of(driver, driver_kw):
 
 
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
-         driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, playout_policy="uniform", **driver_kw):
+         driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, playout_policy="uniform", rollout_prior="uniform",
+         **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
@@ -340,12 +341,19 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     playout_policy (with evaluator="rollout"): how the playouts choose among the legal moves (rp_set_playout_policy) -- "uniform" (the
     default), "area", "width", "width2", "height", "height2", or a pair (w_pow, h_pow): a move of an item (w, h) weighs
     w^w_pow * h^h_pow.  ValueError for anything else and with the network as evaluator.  A driver passed in must have been built
-    with the same policy."""
+    with the same policy.
+    rollout_prior (with evaluator="rollout"): the prior of the search's leaves (rp_set_rollout_prior) -- "uniform" (the default), "low",
+    "low2", "width2", "area", "width2-low2", or a triple (w_pow, h_pow, land_pow): a legal move of an item (w, h) that lands on row t
+    weighs w^w_pow * h^h_pow * (H - t)^land_pow.  ValueError for anything else and with the network as evaluator.  A driver passed in
+    must have been built with the same prior."""
     from .selfplay import BatchedSelfPlay
     _check_instances(item_wh, seeds, initial_board, remaining)
     policy = _lib.playout_policy_powers(playout_policy)
     if policy != (0, 0) and (_evaluator_of(driver, driver_kw) != "rollout"):
         raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
+    prior = _lib.rollout_prior_powers(rollout_prior)
+    if prior != (0, 0, 0) and (_evaluator_of(driver, driver_kw) != "rollout"):
+        raise ValueError("a rollout prior other than 'uniform' needs evaluator='rollout'")
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
@@ -355,11 +363,13 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
         sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
-                             playout_incumbents=bool(playout_incumbents), playout_policy=policy, **driver_kw)
+                             playout_incumbents=bool(playout_incumbents), playout_policy=policy, rollout_prior=prior, **driver_kw)
     elif sp.playout_incumbents != bool(playout_incumbents):
         raise RuntimeError("the driver was built with playout_incumbents=%r" % sp.playout_incumbents)
     elif sp.playout_policy != policy:
         raise RuntimeError("the driver was built with playout_policy=%r" % (sp.playout_policy,))
+    elif sp.rollout_prior != prior:
+        raise RuntimeError("the driver was built with rollout_prior=%r" % (sp.rollout_prior,))
     elif sp.move_rule != rule:
         sp.set_move_rule(rule)
     try:
