@@ -48,7 +48,8 @@ typedef enum rp_status {
     RP_OK = 0,
     RP_ERR_ARG = -1,        /* bad argument */
     RP_ERR_DEVICE = -2,     /* HIP error (no GPU, launch failure, ...) */
-    RP_ERR_CAPACITY = -3,   /* a per-game node / edge / table arena overflowed */
+    RP_ERR_CAPACITY = -3,   /* a per-game node / legal-move / visited-edge arena, the finished-episode ring or the replay buffer
+                               overflowed: a device error, see "device errors" at rp_check */
     RP_ERR_ASSERT = -4,     /* a precondition the reference asserts was violated
                                (BinPackingGame.py:69 item already placed, :89 no legal move) */
     RP_ERR_STATE = -5       /* call not valid in the engine's current phase */
@@ -64,7 +65,7 @@ typedef enum rp_move_rule {
                              * m most-visited actions in ascending order, x from the RP_MOVE_SAMPLE stream of (episode id, move) */
 } rp_move_rule;
 
-/* game phases reported by rp_game_status */
+/* game phases reported by rp_game_status; RP_PHASE_FAILED: a device error stopped this slot's episode (see rp_check) */
 enum { RP_PHASE_IDLE = 0, RP_PHASE_RUNNING = 1, RP_PHASE_WAIT_EVAL = 2, RP_PHASE_MOVE_READY = 3,
        RP_PHASE_EPISODE_DONE = 4, RP_PHASE_FAILED = 5 };
 
@@ -507,14 +508,35 @@ int rp_expand_examples(rp_ctx *ctx, int64_t n, const int64_t *index_dev, int64_t
                        const uint16_t *sp_act_dev, const uint32_t *sp_cnt_dev, float *planes_dev, float *pi_dev, float *value_out_dev);
 /* Every index is checked on the device against E and S (an index list or a pool entry outside the arrays yields a zero row, never a
  * stray access); rp_check synchronises the context's stream and returns the first error device code recorded since the last check
- * (RP_ERR_ARG for such an index, RP_ERR_CAPACITY for an arena overflow), like every synchronising call does. */
+ * (RP_ERR_ARG for such an index, RP_ERR_CAPACITY for an arena overflow), like every synchronising call does.
+ *
+ * Device errors (tests/test_gpu_capacity.py holds the engine to every clause):
+ *  - A kernel that cannot go on records a code; the FIRST code recorded since the last report is kept.  It is returned -- with
+ *    rp_last_error naming the cause -- by the next call that looks for it (rp_check, rp_game_status, rp_search_step with
+ *    n_leaves_out, rp_advance_roots, rp_begin_episodes, rp_begin_pool among them), and by that call only: reporting clears it, the
+ *    call after it returns RP_OK again unless another error has been recorded since.
+ *  - RP_ERR_CAPACITY "node arena" / "legal-move arena" / "visited-edge arena": a slot needed a node beyond node_cap, a run of legal
+ *    moves or a block of visited edges for which its arena had no chunk left.  The caps are exact: an episode whose tree has n nodes
+ *    runs in node_cap = n and fails in n - 1; one whose arenas peak at (P, V) chunks (rp_arena_peak) runs in edge_cap = P chunks and
+ *    vis_cap = V chunks and fails with one chunk fewer in either.  RP_ERR_ASSERT: rp_advance_roots got an action that is no legal move
+ *    of its slot's root.  In both cases the slot is left RP_PHASE_FAILED and takes no further part in rp_search_step; nothing is
+ *    written outside the slot's own arenas, every other slot goes on and computes exactly what it computes without the failure.
+ *    rp_begin_episodes on the slot (or rp_begin_pool) starts it afresh, with a tree like any other's.
+ *  - RP_ERR_CAPACITY "finished-episode ring": episodes ended while the ring already held its max(4 * games, 1024) records.  Their
+ *    records are lost (each reports), the records in the ring stay valid and are popped as usual; the slots go on, and once the ring
+ *    has been popped empty it records again.
+ *  - RP_ERR_CAPACITY "replay buffer": an example found no room.  Past max_examples it is lost: rp_examples_count stays at
+ *    max_examples, the examples recorded before it are intact, and each of them receives the outcome of its own episode and of no
+ *    other.  When only the pool of (action, count) pairs (max_sparse) is full the example is kept without pairs (sp_n = 0, an all-zero
+ *    pi).  The episodes go on.  After rp_examples_clear the buffer records again like one that never overflowed. */
 int rp_check(rp_ctx *ctx);
 
 /* ---- inspection (parity tests) --------------------------------------------------------- */
 /* Sizes of slot g's tree: nodes in use and the span of its legal-move arena (the index range of rp_dump_tree's edge arrays). */
 int rp_tree_size(rp_ctx *ctx, int32_t slot, int32_t *n_nodes_out, int32_t *n_edges_out);
 /* High-water marks of the level arenas over all slots since create: chunks in use (legal-move runs, visited blocks) and
- * the chunk sizes in entries (6 and 32 bytes per entry).  Sizing aid for edge_cap / vis_cap. */
+ * the chunk sizes in entries (6 and 32 bytes per entry).  Sizing aid for edge_cap / vis_cap: the same episodes run in exactly that
+ * many chunks of each kind and in no fewer (see "device errors" at rp_check). */
 int rp_arena_peak(rp_ctx *ctx, int32_t *prior_chunks_out, int32_t *visited_chunks_out, int32_t *chunk_entries_out2);
 /* Host copy of slot g's tree.  Node i: rows u64[H], remaining u8[N], term i8 (0 / +-1 = Es),
  * term_kind u8, expanded u8, ns u32, edge_off u32, n_valid u32.  Edge e (one per legal move, dense view of the sparse

@@ -180,7 +180,7 @@ struct DP {  // device view of a context, passed by value to every kernel
     int *ex_value;    // ranked outcome of the episode, 0 until it ends
     u64 *ex_episode;  // episode id and move number of every example: the buffer fills in completion order across slots,
     int *ex_move;     // the reference appends episode by episode, move by move (CoachBPP.py:80,133)
-    u32 *slot_ex;     // [G][N] example indices of the running episode
+    u32 *slot_ex;     // [G][N] example indices of the running episode (NONE32: the move's example found no room)
     // evaluator stem (first convolution + max-pool computed from the packed state)
     int *stemT, *stemTB, *stemBias;  // [N][25][16], [512][16], [16]: tap sums in per-channel fixed point (k_stem_tables)
     float *stemScale;                // [16] value of one fixed-point unit of channel o (a power of two)
@@ -1254,27 +1254,32 @@ __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u3
         if (lane == 0) { idx = atomicAdd(p.ex_count, 1ull); sp = atomicAdd(p.ex_sp_cursor, (unsigned long long)n_sp); }
         idx = __shfl(idx, 0); sp = __shfl(sp, 0);
         int mv = p.moves[g];
-        if ((long long)idx < p.max_examples && mv < p.N && (long long)(sp + n_sp) <= p.sp_cap) {
+        // An example that got an index is always a whole record (rp_examples_count counts it): without its pairs when the pool of
+        // pairs is full.  One that got no index is lost, and the slot's entry says so -- the entry of the slot's previous episode
+        // would otherwise receive this episode's outcome (finish_episode_impl).
+        const bool has_index = (long long)idx < p.max_examples && mv < p.N, has_pairs = (long long)(sp + n_sp) <= p.sp_cap;
+        if (has_index) {
             const u32 *k = t.key + (size_t)root * p.KW;
             u32 *ek = p.ex_key + (size_t)idx * p.KW;
             for (int q = lane; q < p.KW; q += 64) ek[q] = k[q];
             u8 *ew = p.ex_wh + (size_t)idx * p.N * 2;
             for (int q = lane; q < 2 * p.N; q += 64) ew[q] = t.wh[q];
-            if (p.onehot_examples) {
+            if (has_pairs && p.onehot_examples) {
                 if (lane == 0) { p.ex_sp_act[sp] = (u16)chosen_action; p.ex_sp_cnt[sp] = 1u; }
-            } else {
+            } else if (has_pairs) {
                 for (u32 q = lane; q < n_sp; q += 64) {
                     p.ex_sp_act[sp + q] = t.pAct[hd.prior_off + t.vis[hd.vis_off + q].idx];
                     p.ex_sp_cnt[sp + q] = t.vis[hd.vis_off + q].n & NSA_MASK;
                 }
             }
             if (lane == 0) {
-                p.ex_sp_off[idx] = (u32)sp; p.ex_sp_n[idx] = n_sp;
+                p.ex_sp_off[idx] = has_pairs ? (u32)sp : 0u; p.ex_sp_n[idx] = has_pairs ? n_sp : 0u;
                 p.ex_value[idx] = 0; p.ex_episode[idx] = p.episode[g]; p.ex_move[idx] = mv; p.slot_ex[(size_t)g * p.N + mv] = (u32)idx;
             }
-        } else if (lane == 0) {
-            set_error(p, ERR_EXAMPLES_CAP);
+        } else if (lane == 0 && mv < p.N) {
+            p.slot_ex[(size_t)g * p.N + mv] = NONE32;
         }
+        if (lane == 0 && !(has_index && has_pairs)) set_error(p, ERR_EXAMPLES_CAP);
     }
     u64 filled = 0;  // wave-uniform, like chosen_action: the episode's end below takes this move's entry from the registers
     if (p.tr_action) {  // placement trace: the rows the move filled are those where the child's key differs from the root's
