@@ -41,8 +41,9 @@ extern "C" {
                              9: initial states of pool instances (rp_set_instance_initial)
                              10: incumbents (rp_set_incumbent, rp_pop_finished_best, rp_incumbents); additive, same number: playout
                                  incumbents (rp_set_incumbent_playouts, rp_pop_finished_best_playouts, rp_incumbent_sources, rp_rollout_paths), the
-                                 playout policy (rp_set_playout_policy, rp_playout_policy) and the rollout prior (rp_set_rollout_prior,
-                                 rp_rollout_prior, rp_rollout_prior_states) */
+                                 playout policy (rp_set_playout_policy, rp_playout_policy), the rollout prior (rp_set_rollout_prior,
+                                 rp_rollout_prior, rp_rollout_prior_states) and the playouts' landing power (rp_set_playout_landing,
+                                 rp_playout_landing) */
 
 typedef enum rp_status {
     RP_OK = 0,
@@ -385,6 +386,30 @@ int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, const uint8_t
 int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow);
 /* The powers in force (either pointer may be NULL). */
 int rp_playout_policy(const rp_ctx *ctx, int32_t *w_pow_out, int32_t *h_pow_out);
+/* The landing power of the playouts: a setting of its own beside the playout policy, land_pow in {0, 1, 2}, default 0.  It lets a
+ * playout (MCTS_bpp.py:87) weigh a legal move by the row it lands on as well as by its item.  At step s of playout j, on the
+ * playout's current board:
+ *   - m_i is the legal-column mask of item i (getValidMoves, BinPackingGame.py:78-92).  No legal move ends the playout.
+ *   - wt_i = w_i^w_pow * h_i^h_pow comes from the playout policy in force, unchanged.
+ *   - L(i, c) = (H - t(w_i, c))^land_pow, t(w, c) the first row whose window [c, c + w) is empty, H - 1 if none is: the t of the
+ *     rollout prior below (BinPackingLogic.py:66-68).  1 <= L <= 4096.
+ *   - R_i = sum of L(i, c) over c in m_i <= 64 * 4096 = 2^18.  S_i = wt_i * R_i <= 2^30.
+ *   - T = sum S_i <= 128 * 2^30 = 2^37: a 64-bit integer sum.
+ *   - pick = umulhi(sample(h0, j, s), T), the same stream: h0 = mix64(key_hash(S, seed) ^ e).
+ *   - item   = the first i whose inclusive sum sum_{k<=i} S_k exceeds pick;
+ *     q      = floor((pick - sum_{k<i} S_k) / wt_i), so q < R_i;
+ *     column = the first legal column c of the item, ascending, whose inclusive sum of L(i, .) over the item's legal columns up to c
+ *              exceeds q.
+ *     Equivalently, each move owns wt_i * L(i, c) consecutive units of [0, T) in ascending action order.
+ *   - With land_pow == 0, L = 1: the rule of the playout policy above, bit for bit.
+ * Everything else about a playout is unchanged: h0, its outcome and score, the tie rule, the bound of N steps, the independence from
+ * slot, row and launch, and the replay of a winning playout in the playout offers under the setting that scored it.
+ * RP_ERR_ARG outside 0..2; RP_ERR_STATE while any slot is in the middle of an episode, as rp_set_playout_policy; a refused call changes
+ * nothing.  Applies to rp_rollout_eval, rp_rollout_states, rp_rollout_paths and the playout offers from then on.  Kernel arguments are
+ * baked into captured graphs: re-capture after switching. */
+int rp_set_playout_landing(rp_ctx *ctx, int32_t land_pow);
+/* The power in force (the pointer may be NULL). */
+int rp_playout_landing(const rp_ctx *ctx, int32_t *land_pow_out);
 /* The rollout prior of the context: the pi that rp_rollout_eval returns in place of nnet.predict's (MCTS_bpp.py:87).  Three small
  * integer powers (w_pow, h_pow, land_pow).  The default (0, 0, 0) is the uniform prior above.  The rule:
  *   - For a leaf state, m_i is the legal-column mask of item i (getValidMoves, BinPackingGame.py:78-92).

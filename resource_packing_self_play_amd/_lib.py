@@ -69,6 +69,8 @@ _SIGS = {
     "rp_incumbent_sources": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "rp_set_playout_policy": (C.c_int, [_vp, _i32, _i32]),
     "rp_playout_policy": (C.c_int, [_vp, _vp, _vp]),
+    "rp_set_playout_landing": (C.c_int, [_vp, _i32]),
+    "rp_playout_landing": (C.c_int, [_vp, _vp]),
     "rp_set_rollout_prior": (C.c_int, [_vp, _i32, _i32, _i32]),
     "rp_rollout_prior": (C.c_int, [_vp, _vp, _vp, _vp]),
     "rp_rollout_prior_states": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
@@ -144,6 +146,15 @@ def playout_policy_powers(policy):
     if not ok or w_pow < 0 or h_pow < 0 or w_pow + h_pow > 2:
         raise ValueError("playout policy %r: a name or a pair of integers (w_pow, h_pow), w_pow >= 0, h_pow >= 0, w_pow + h_pow <= 2" % (policy,))
     return int(w_pow), int(h_pow)
+
+
+def playout_landing_power(land_pow):
+    """The landing power of the playouts (rp_set_playout_landing) as an int: 0, 1 or 2; None is 0.  ValueError for anything else."""
+    if land_pow is None:
+        return 0
+    if not isinstance(land_pow, (int, np.integer)) or isinstance(land_pow, bool) or not 0 <= land_pow <= 2:
+        raise ValueError("playout landing power %r: an integer 0, 1 or 2" % (land_pow,))
+    return int(land_pow)
 
 # names of the rollout priors (rp_set_rollout_prior): the powers (w_pow, h_pow, land_pow) of a legal move's weight
 # w^w_pow * h^h_pow * (H - t)^land_pow, t = the first row whose window under the item is empty
@@ -396,6 +407,18 @@ class Engine:
         w, h = _i32(0), _i32(0)
         self._ck(self.L.rp_playout_policy(self.h, C.byref(w), C.byref(h)))
         return int(w.value), int(h.value)
+
+    def set_playout_landing(self, land_pow):
+        """Landing power of the playouts (rp_set_playout_landing): a legal move (i, c) weighs (H - t)^land_pow times the playout
+        policy's weight, t the first row whose window under the item is empty; 0 is off.  Refused outside 0..2 and while a slot is in
+        mid-episode; re-capture graphs after switching."""
+        self._ck(self.L.rp_set_playout_landing(self.h, int(land_pow)))
+
+    def playout_landing(self):
+        """The landing power in force (rp_playout_landing)."""
+        t = _i32(0)
+        self._ck(self.L.rp_playout_landing(self.h, C.byref(t)))
+        return int(t.value)
 
     def set_rollout_prior(self, w_pow, h_pow, land_pow):
         """Rollout prior (rp_set_rollout_prior): rollout_eval's pi rows weigh a legal move (i, c) by w_i^w_pow * h_i^h_pow *

@@ -204,6 +204,11 @@ struct DP {  // device view of a context, passed by value to every kernel
     u8 *inc;       // [G] running episodes
     u8 *fin_inc;   // [fin_cap] finished episodes, at the ring index of their record
     int inc_stride;
+    // landing power of the playouts (rp_set_playout_landing): move (i, c) weighs (H - t(w_i, c))^land_pow times the policy's weight
+    // (pol_w, pol_h below).  0 = off: the host then launches the uniform or the item-weighted instantiations, which never read it.  It
+    // sits in the four bytes of padding behind inc_stride, not beside the policy: the struct's size and every kernel's argument offsets
+    // stay what they were -- appended, it cost the item-weighted k_rollout with playout offers one more spilled scalar register.
+    int land_pow;
     IncNew *inc_new;  // [G] k_search's new terminal, not offered yet
     // playout incumbents (rp_set_incumbent_playouts): where each record came from, (tree_moves, playout) per slot and, behind them, per
     // ring entry.  NULL while the mode is off: k_rollout then takes one uniform branch and the tree offers write nothing more.
@@ -2534,7 +2539,23 @@ __device__ __forceinline__ int policy_weight(int w, int h, int pol_w, int pol_h)
 // number (pick - the sum before it) / wt_i -- one division of wave-uniform values.  The weights depend on the item alone, so they are
 // one register per lane (two for N > 64), set before the loop.  T needs both halves' scans before the draw; the uniform form knows
 // its total, nv, from gen_valid_moves and scans the second half only when the pick falls there.  Without WT this is the uniform code.
-template <typename row_t, bool BIG, bool REC = false, bool WT = false>
+// PM == PLAY_ITEM is WT.  PM == PLAY_LAND: the landing power of the context on top of the policy (rp_set_playout_landing, p.land_pow in 1..2).  Move (i, c)
+// weighs wt_i * L(i, c), L(i, c) = (H - t(w_i, c))^land_pow, t = the first row whose window [c, c + w_i) is empty, H - 1 if none is
+// (get_adjacency's t, BinPackingLogic.py:66-68): 1 <= L <= 4096.  R_i = sum of L over the item's legal columns <= 2^18, S_i = wt_i * R_i
+// <= 2^30 still fits a register, T = sum S_i <= 2^37 does not: the item scan runs on the two 15-bit halves of S_i and is joined in 64
+// bits.  The board is needed inside the step, and it is taken transposed: lane c holds column c's cells as a mask over the rows (H
+// readlanes, what gen_valid_moves pays for its column counts), O_w(c) = O_(w-1)(c) | column (c + w - 1) is one lane shift per width, and
+// t(w, c) is the first zero bit of O_w(c) below H -- no ballot per (width, column).  For every width that an item with a legal move
+// has, lanes = items of that width walk their masks and fetch L from lanes = columns, one bpermute per trip, at most popcount(m_i)
+// trips; nothing goes through LDS, so the workgroup's LDS is the uniform kernel's.  The picked item's column is found by a wave-uniform
+// walk over its legal columns that forms t again from the rows, one ballot per column passed: q = floor(unit / wt_i) < R_i, and the walk
+// stops at the item's last legal column whether or not that holds.
+enum { PLAY_UNIFORM = 0, PLAY_ITEM = 1, PLAY_LAND = 2 };
+__device__ __forceinline__ u32 wave_shift_down1(u32 v) { return dpp_or_zero<0x130, 0xf>(v); }  // lane l reads lane l + 1 (wave_shl:1), lane 63 reads 0
+__device__ __forceinline__ u64 wave_shift_down1(u64 v) { return ((u64)wave_shift_down1((u32)(v >> 32)) << 32) | wave_shift_down1((u32)v); }
+// inclusive scan, ascending lanes, of values <= 2^30 whose sum needs 64 bits: each 15-bit half sums to 2^21 at most
+__device__ __forceinline__ u64 wave_scan_add_wide(u32 v) { return ((u64)wave_scan_add(v >> 15) << 15) + (u64)wave_scan_add(v & 0x7FFFu); }
+template <typename row_t, bool BIG, bool REC = false, int PM = PLAY_UNIFORM>
 __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row_t &myrow, u64 &rem0, u64 &rem1, u64 h0, u64 j, u64 *vm, u16 *act_out = nullptr,
                               int act_cap = 0) {
     const int lane = lane_id(), N = p.N;
@@ -2542,8 +2563,9 @@ __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row
     ValidSink sink;
     sink.act = nullptr; sink.mask = nullptr; sink.cap = 0; sink.vm = vm;
     sink.have_sizes = 1; sink.w_lo = z.w_lo; sink.h_lo = z.h_lo; sink.w_hi = z.w_hi; sink.h_hi = z.h_hi;
+    constexpr bool WT = PM == PLAY_ITEM;
     int wt_lo = 1, wt_hi = 1;
-    if (WT) {
+    if (PM != PLAY_UNIFORM) {
         wt_lo = policy_weight(z.w_lo, z.h_lo, p.pol_w, p.pol_h);
         if (big) wt_hi = policy_weight(z.w_hi, z.h_hi, p.pol_w, p.pol_h);
     }
@@ -2578,6 +2600,65 @@ __device__ int random_playout(const DP &p, const u8 *wh, const ItemSizes &z, row
                 own = uni(__shfl(m_hi, l));
             }
             skip = (int)((u32)unit / (u32)wt);  // wt >= 1: the owning item has a legal column, so its lane holds an item
+        } else if (PM == PLAY_LAND) {
+            const int H = p.H;
+            u64 colm = 0ull;  // lane c: bit r = cell (r, c); the rows hold no bit at or above W
+            for (int r = 0; r < H; ++r) colm |= (((u64)RowOps<row_t>::at(myrow, r) >> lane) & 1ull) << r;
+            u64 O = colm, nxt = colm;
+            u32 R_lo = 0, R_hi = 0;
+            u64 todo = __ballot(m_lo != 0ull || m_hi != 0ull);  // lanes whose items' widths are still to come
+            for (int w = 1; w <= p.W && todo; ++w) {
+                if (w > 1) { nxt = wave_shift_down1(nxt); O |= nxt; }  // O_w(c): the rows occupied in [c, c + w)
+                const bool mine_lo = m_lo != 0ull && z.w_lo == w, mine_hi = big && m_hi != 0ull && z.w_hi == w;
+                const u64 now = __ballot(mine_lo || mine_hi);
+                if (now == 0ull) continue;
+                const u64 lo_left = __ballot(m_lo != 0ull && z.w_lo > w), hi_left = big ? __ballot(m_hi != 0ull && z.w_hi > w) : 0ull;
+                todo = lo_left | hi_left;
+                const u64 free_rows = ~O & full_mask(H);
+                const int t = free_rows ? __ffsll((long long)free_rows) - 1 : H - 1;  // no empty row: t = H - 1 (:66-68)
+                const int L = policy_power(H - t, p.land_pow);
+                u64 r_lo = mine_lo ? m_lo : 0ull, r_hi = mine_hi ? m_hi : 0ull;
+                while (__ballot((r_lo | r_hi) != 0ull)) {  // every trip clears one bit of every mask that is left: at most 64 trips
+                    const int v_lo = __shfl(L, r_lo ? __ffsll((long long)r_lo) - 1 : 0);
+                    if (r_lo) { R_lo += (u32)v_lo; r_lo &= r_lo - 1; }
+                    if (big) {
+                        const int v_hi = __shfl(L, r_hi ? __ffsll((long long)r_hi) - 1 : 0);
+                        if (r_hi) { R_hi += (u32)v_hi; r_hi &= r_hi - 1; }
+                    }
+                }
+            }
+            const u32 S_lo = (u32)wt_lo * R_lo, S_hi = big ? (u32)wt_hi * R_hi : 0u;  // <= 4096 * 2^18; 0 on lanes without a legal move
+            const u64 inc_lo = wave_scan_add_wide(S_lo);
+            const u64 tot_lo = RowOps<u64>::at(inc_lo, 63);
+            u64 inc_hi = 0ull, total = tot_lo;
+            if (big) { inc_hi = wave_scan_add_wide(S_hi); total += RowOps<u64>::at(inc_hi, 63); }
+            const u64 pick = __umul64hi(sample_u64(h0, j, (u64)s), total);  // 0 <= pick < total <= 2^37
+            u32 unit;
+            int wt;
+            if (pick < tot_lo) {
+                const int l = __ffsll((long long)__ballot(pick < inc_lo)) - 1;  // first item whose inclusive sum exceeds pick
+                item = l;
+                unit = (u32)(pick - (RowOps<u64>::at(inc_lo, l) - (u64)(u32)__builtin_amdgcn_readlane((int)S_lo, l)));
+                wt = __builtin_amdgcn_readlane(wt_lo, l);
+                own = uni(__shfl(m_lo, l));
+            } else {
+                const u64 q2 = pick - tot_lo;
+                const int l = __ffsll((long long)__ballot(q2 < inc_hi)) - 1;
+                item = 64 + l;
+                unit = (u32)(q2 - (RowOps<u64>::at(inc_hi, l) - (u64)(u32)__builtin_amdgcn_readlane((int)S_hi, l)));
+                wt = __builtin_amdgcn_readlane(wt_hi, l);
+                own = uni(__shfl(m_hi, l));
+            }
+            u32 q = unit / (u32)wt;  // < R_item
+            const int wi = item < 64 ? __builtin_amdgcn_readlane(z.w_lo, item & 63) : __builtin_amdgcn_readlane(z.w_hi, item & 63);
+            while (own & (own - 1)) {  // at most popcount(own) - 1 trips: the last legal column is taken without a test
+                const u64 e = __ballot(lane < H && (myrow & window<row_t>(__ffsll((long long)own) - 1, wi, p.W)) == 0);
+                const u32 L = (u32)policy_power(H - (e ? __ffsll((long long)e) - 1 : H - 1), p.land_pow);
+                if (q < L) break;
+                q -= L;
+                own &= own - 1;
+            }
+            skip = 0;
         } else {
             const int pick = (int)__umul64hi(sample_u64(h0, j, (u64)s), (u64)nv);  // 0 <= pick < nv
             const int inc_lo = (int)wave_scan_add((u32)__popcll(m_lo));
@@ -2619,7 +2700,7 @@ __device__ int playout_outcome(const DP &p, row_t myrow, u64 rem0, u64 rem1, int
 // strictly greater -- so the same leaf offered twice changes nothing.  The winner is then played again from the leaf, a function of
 // (h0, j) alone, with the action sink pointed behind the head of the list (played moves, then the leaf's path as k_search stored it for
 // the commit), and its final state is the record's board and outcome.  One wave, all lanes; every lane holds the same r and j.
-template <typename row_t, bool BIG, bool WT>
+template <typename row_t, bool BIG, int PM>
 __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
     const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
     const int lane = lane_id();
@@ -2644,7 +2725,7 @@ __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
     const ItemSizes z = load_item_sizes<BIG>(t.wh, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ p.episode[g]);
     const int room = tree_moves < p.N ? p.N - tree_moves : 0;  // every move places one item: the list never outgrows N
-    const int m = random_playout<row_t, BIG, true, WT>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, vm, rec.action() + (tree_moves < p.N ? tree_moves : 0), room);
+    const int m = random_playout<row_t, BIG, true, PM>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, vm, rec.action() + (tree_moves < p.N ? tree_moves : 0), room);
     double r_again;
     const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, p.total_area[g], p.max_h[g], p.has_buf[g] != 0, p.bl[g], &r_again);
     incumbent_lead(p, t, rec, prefix, depth, pe0, pn0, pe1, pn1);
@@ -2665,7 +2746,7 @@ __device__ void playout_offer(const DP &p, int g, double r, int j, u64 *vm) {
 // (playout_offer).  The host chooses the instantiation, one uniform branch per launch: as a run-time branch inside one kernel the offer
 // took k_rollout from 8 waves per SIMD to 7 and made it spill scalar registers with the mode off too (make resource-usage), so the
 // kernel of the mode that is off stays the code it was.
-template <typename row_t, bool BIG, bool TRACK, bool WT>
+template <typename row_t, bool BIG, bool TRACK, int PM>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int playouts, float *pi, float *v, long long capacity_rows) {
     const int b = blockIdx.x, wv = wave_in_block();
     if (b >= (p.rows_identity ? p.G : *p.eval_count) || b >= capacity_rows) return;
@@ -2687,7 +2768,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
     double best_r = 0.0;
     for (int j = wv; j < playouts; j += WAVES_PER_BLOCK) {
         row_t myrow = leaf; u64 rem0 = l0, rem1 = l1;
-        random_playout<row_t, BIG, false, WT>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
+        random_playout<row_t, BIG, false, PM>(p, t.wh, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wv]);
         double r;
         sum += playout_outcome<row_t>(p, myrow, rem0, rem1, area, max_h, has_buf, bl, &r);
         if (TRACK && (best_j < 0 || r > best_r)) { best_r = r; best_j = j; }
@@ -2715,12 +2796,12 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout(DP p, int play
             const int jk = s_best_j[k];
             if (jk >= 0 && (rk > r || (rk == r && jk < j))) { r = rk; j = jk; }
         }
-        playout_offer<row_t, BIG, WT>(p, g, r, uni(j), s_vm[0]);
+        playout_offer<row_t, BIG, PM>(p, g, r, uni(j), s_vm[0]);
     }
 }
 // The action lists of the playouts k_rollout_states plays, through the recording path of the playout offers: one wave per (state,
 // playout), zeros past the playout's moves.
-template <typename row_t, bool BIG, bool WT>
+template <typename row_t, bool BIG, int PM>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_paths(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh, const u64 *episode,
                                                                          u16 *action, int *moves_out) {
     const long long idx = (long long)blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
@@ -2734,13 +2815,13 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_paths(DP p, lo
     const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
     u16 *mine = action + idx * p.N;
-    const int moves = random_playout<row_t, BIG, true, WT>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()], mine, p.N);
+    const int moves = random_playout<row_t, BIG, true, PM>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()], mine, p.N);
     for (int q = lane; q < p.N; q += 64)
         if (q >= moves) mine[q] = (u16)0;
     if (lane == 0) moves_out[idx] = moves;
 }
 // The stateless batch form: one wave per (state, playout) of B host states, K playouts each.
-template <typename row_t, bool BIG, bool WT>
+template <typename row_t, bool BIG, int PM>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, long long B, int playouts, const u64 *rows, const u8 *rem, const u8 *wh,
                                                                           const int *area, const int *max_h, const u64 *episode, int has_buf, double bl,
                                                                           int *outcome, double *score, int *moves_out, u64 *board) {
@@ -2754,7 +2835,7 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_rollout_states(DP p, l
     const u8 *w2 = wh + b * p.N * 2;
     const ItemSizes z = load_item_sizes<BIG>(w2, p.N);
     const u64 h0 = mix64(key_hash<row_t>(myrow, p.H, p.N, rem0, rem1, p.seed) ^ (episode ? episode[b] : 0ull));
-    const int moves = random_playout<row_t, BIG, false, WT>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()]);
+    const int moves = random_playout<row_t, BIG, false, PM>(p, w2, z, myrow, rem0, rem1, h0, (u64)j, s_vm[wave_in_block()]);
     double r;
     const int e = playout_outcome<row_t>(p, myrow, rem0, rem1, area[b], max_h[b], has_buf != 0, bl, &r);
     if (lane == 0) { outcome[idx] = e; score[idx] = r; moves_out[idx] = moves; }
@@ -5333,9 +5414,15 @@ extern "C" int rp_game_ended(rp_ctx *ctx, int64_t B, const uint64_t *rows, const
 }
 
 #define RP_MAX_PLAYOUTS 256
-// The rollout kernels come in a uniform and a weighted form (random_playout's WT): the host picks one per launch, so the uniform
-// kernels are the code they were before the policy existed.
-static bool weighted_playouts(const DP &d) { return d.pol_w != 0 || d.pol_h != 0; }
+// The rollout kernels come in a uniform, an item-weighted and a landing form (random_playout's PM): the host picks one per launch, so
+// the uniform kernels are the code they were before the policy existed, and both older forms the code they were before the landing power.
+static int playout_mode(const DP &d) { return d.land_pow != 0 ? PLAY_LAND : (d.pol_w != 0 || d.pol_h != 0) ? PLAY_ITEM : PLAY_UNIFORM; }
+// fn(std::integral_constant<int, PM>) for the mode in force -> the kernel's pointer
+template <class Pick> static auto by_playout_mode(const DP &d, Pick pick) {
+    const int pm = playout_mode(d);
+    return pm == PLAY_LAND ? pick(std::integral_constant<int, PLAY_LAND>{}) : pm == PLAY_ITEM ? pick(std::integral_constant<int, PLAY_ITEM>{})
+                                                                                                : pick(std::integral_constant<int, PLAY_UNIFORM>{});
+}
 static bool heuristic_prior(const rp_ctx *ctx) { return ctx->prior.w_pow != 0 || ctx->prior.h_pow != 0 || ctx->prior.land_pow != 0; }
 
 extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, float *v_dev, int64_t capacity_rows) {
@@ -5352,8 +5439,9 @@ extern "C" int rp_rollout_eval(rp_ctx *ctx, int32_t playouts, float *pi_dev, flo
         if (rc != RP_OK) return rc;
         pi_dev = nullptr;
     }
-    const auto fn = d.inc_src ? (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, false>))
-                              : (weighted_playouts(d) ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, true>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, false>));
+    const auto fn = by_playout_mode(d, [&](auto pm) {
+        return d.inc_src ? GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, true, decltype(pm)::value>) : GEO_KERNEL(ctx, big, k_rollout<row_t, geo.flag, false, decltype(pm)::value>);
+    });
     return launch(ctx, "k_rollout", fn, dim3((unsigned)rows), dim3(64 * WAVES_PER_BLOCK), 0, d, playouts, pi_dev, v_dev, capacity_rows);
 }
 
@@ -5384,7 +5472,7 @@ extern "C" int rp_rollout_states(rp_ctx *ctx, int64_t B, const uint64_t *rows, c
     int *dmoves = s.out(moves_out, n);
     u64 *dboard = board_out ? s.out((u64 *)board_out, n * d.H) : nullptr;
     int rc = s.ok();
-    const auto fn = weighted_playouts(d) ? GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag, true>) : GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag, false>);
+    const auto fn = by_playout_mode(d, [&](auto pm) { return GEO_KERNEL(ctx, d.N > 64, k_rollout_states<row_t, geo.flag, decltype(pm)::value>); });
     if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_states", fn, (long long)n, d, B, playouts, drows, drem, dwh, darea, dmh, dep, has ? 1 : 0, bl, dout, dscore, dmoves, dboard);
     return rc == RP_OK ? s.finish() : rc;
 }
@@ -5406,7 +5494,7 @@ extern "C" int rp_rollout_paths(rp_ctx *ctx, int64_t B, const uint64_t *rows, co
     u16 *dact = s.out((u16 *)action_out, n * d.N);
     int *dmoves = s.out(moves_out, n);
     int rc = s.ok();
-    const auto fn = weighted_playouts(d) ? GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, true>) : GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, false>);
+    const auto fn = by_playout_mode(d, [&](auto pm) { return GEO_KERNEL(ctx, d.N > 64, k_rollout_paths<row_t, geo.flag, decltype(pm)::value>); });
     if (rc == RP_OK) rc = launch_waves(ctx, "k_rollout_paths", fn, (long long)n, d, B, playouts, drows, drem, dwh, dep, dact, dmoves);
     return rc == RP_OK ? s.finish() : rc;
 }
@@ -5641,6 +5729,24 @@ extern "C" int rp_set_playout_policy(rp_ctx *ctx, int32_t w_pow, int32_t h_pow) 
     if (rc != RP_OK) return rc;
     if (g >= 0) return fail(ctx, RP_ERR_STATE, "rp_set_playout_policy: slot %d is in the middle of an episode; switch the policy between pools", g);
     d.pol_w = w_pow; d.pol_h = h_pow;
+    return RP_OK;
+}
+
+extern "C" int rp_set_playout_landing(rp_ctx *ctx, int32_t land_pow) {
+    if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_playout_landing: bad argument");
+    if (land_pow < 0 || land_pow > 2) return fail(ctx, RP_ERR_ARG, "rp_set_playout_landing: power %d outside 0..2", land_pow);
+    // not while episodes are being played: an incumbent's record would stop being a function of the search alone
+    int g = -1;
+    const int rc = slot_in_episode(ctx, &g);
+    if (rc != RP_OK) return rc;
+    if (g >= 0) return fail(ctx, RP_ERR_STATE, "rp_set_playout_landing: slot %d is in the middle of an episode; switch the policy between pools", g);
+    ctx->d.land_pow = land_pow;
+    return RP_OK;
+}
+
+extern "C" int rp_playout_landing(const rp_ctx *ctx, int32_t *land_pow_out) {
+    if (!ctx) return RP_ERR_ARG;
+    if (land_pow_out) *land_pow_out = ctx->d.land_pow;
     return RP_OK;
 }
 

@@ -13,6 +13,7 @@ own engine context, HIP stream and captured HIP graph of one simulation WAVE:
 With evaluator="rollout" the two middle steps are one kernel, rp_rollout_eval: every waiting leaf's value is the mean outcome of
 `playouts` uniform random playouts and its prior is uniform -- plain MCTS with no network, the baseline a trained net is compared with.
 playout_policy weighs a playout's legal moves by their item's size (rp_set_playout_policy); the default is uniform.
+playout_landing weighs them by the row they land on as well (rp_set_playout_landing); the default, 0, is off.
 rollout_prior replaces the uniform prior by one that weighs a legal move by its item's size and the row it lands on
 (rp_set_rollout_prior); the default is uniform.
 
@@ -50,6 +51,8 @@ class _Group:
             self.eng.set_incumbent_playouts(True)
         if owner.playout_policy != (0, 0):
             self.eng.set_playout_policy(*owner.playout_policy)
+        if owner.playout_landing != 0:
+            self.eng.set_playout_landing(owner.playout_landing)
         self.prior = owner.rollout_prior != (0, 0, 0)
         if self.prior:
             self.eng.set_rollout_prior(*owner.rollout_prior)
@@ -142,7 +145,7 @@ class BatchedSelfPlay:
     def __init__(self, game, nnet, args, games, move_rule=_lib.MOVE_SAMPLE, seed=0, node_cap=0, edge_cap=0, max_examples=0,
                  use_graph=True, groups=2, step_cap=4, use_stem=True, fuse_elementwise=True, dense_small_convs=True, reclaim=True, vis_cap=0, compact_rows=True, channels_last=True, resblock_kernel=True, device=None,
                  tie_salt=None, host_evaluator=None, record_packings=False, wide_logits=True, evaluator="cnn", playouts=8, record_best=False,
-                 playout_incumbents=False, playout_policy="uniform", rollout_prior="uniform"):
+                 playout_incumbents=False, playout_policy="uniform", rollout_prior="uniform", playout_landing=0):
         """evaluator: "cnn" (the network, the default) or "rollout": no network at all -- a leaf's value is the mean outcome of `playouts`
         uniform random playouts on the device (rp_rollout_eval) and its prior is uniform; nnet may then be None, the device is `device`
         or the current one, and the wave (search, playouts, commit) is captured into the HIP graph like the CNN wave.  Playouts are ranked
@@ -160,6 +163,9 @@ class BatchedSelfPlay:
         playout_policy: with evaluator="rollout", how a playout chooses among the legal moves (rp_set_playout_policy): a name of
         _lib.PLAYOUT_POLICIES or a pair (w_pow, h_pow) -- a move of an item (w, h) weighs w^w_pow * h^h_pow.  "uniform" (the default)
         is (0, 0).  ValueError for anything else, and for a non-uniform policy with another evaluator.
+        playout_landing: with evaluator="rollout", the landing power of the playouts (rp_set_playout_landing): 0 (the default), 1 or 2 --
+        a legal move that lands on row t weighs (H - t)^playout_landing times its weight under playout_policy.  ValueError for anything
+        else, and for a non-zero power with another evaluator.
         rollout_prior: with evaluator="rollout", the prior of a leaf (rp_set_rollout_prior): a name of _lib.ROLLOUT_PRIORS or a triple
         (w_pow, h_pow, land_pow) -- a legal move of an item (w, h) that lands on row t weighs w^w_pow * h^h_pow * (H - t)^land_pow.
         "uniform" (the default) is (0, 0, 0).  ValueError for anything else, and for a non-uniform prior with another evaluator.
@@ -199,6 +205,9 @@ class BatchedSelfPlay:
         self.playout_policy = _lib.playout_policy_powers(playout_policy)  # likewise
         if self.playout_policy != (0, 0) and not rollout:
             raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
+        self.playout_landing = _lib.playout_landing_power(playout_landing)  # likewise
+        if self.playout_landing != 0 and not rollout:
+            raise ValueError("a playout landing power other than 0 needs evaluator='rollout'")
         self.rollout_prior = _lib.rollout_prior_powers(rollout_prior)  # likewise
         if self.rollout_prior != (0, 0, 0) and not rollout:
             raise ValueError("a rollout prior other than 'uniform' needs evaluator='rollout'")

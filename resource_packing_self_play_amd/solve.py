@@ -311,7 +311,7 @@ def _evaluator_of(driver, driver_kw):
 
 def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None, rewards_list=(), total_area=None, bin_w=None, games=None,
          driver=None, seed=0, initial_board=None, remaining=None, best=False, playout_incumbents=False, playout_policy="uniform", rollout_prior="uniform",
-         **driver_kw):
+         playout_landing=0, **driver_kw):
     """Packs every instance with `nnet` guiding args.numMCTSSims simulations per move -> list[Packing] in instance order
     (episode_id = the instance's index).
 
@@ -342,6 +342,9 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     default), "area", "width", "width2", "height", "height2", or a pair (w_pow, h_pow): a move of an item (w, h) weighs
     w^w_pow * h^h_pow.  ValueError for anything else and with the network as evaluator.  A driver passed in must have been built
     with the same policy.
+    playout_landing (with evaluator="rollout"): the landing power of the playouts (rp_set_playout_landing) -- 0 (the default), 1 or 2: a
+    legal move that lands on row t weighs (H - t)^playout_landing times its weight under playout_policy.  ValueError for anything else
+    and with the network as evaluator.  A driver passed in must have been built with the same power.
     rollout_prior (with evaluator="rollout"): the prior of the search's leaves (rp_set_rollout_prior) -- "uniform" (the default), "low",
     "low2", "width2", "area", "width2-low2", or a triple (w_pow, h_pow, land_pow): a legal move of an item (w, h) that lands on row t
     weighs w^w_pow * h^h_pow * (H - t)^land_pow.  ValueError for anything else and with the network as evaluator.  A driver passed in
@@ -351,6 +354,9 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     policy = _lib.playout_policy_powers(playout_policy)
     if policy != (0, 0) and (_evaluator_of(driver, driver_kw) != "rollout"):
         raise ValueError("a playout policy other than 'uniform' needs evaluator='rollout'")
+    landing = _lib.playout_landing_power(playout_landing)
+    if landing != 0 and (_evaluator_of(driver, driver_kw) != "rollout"):
+        raise ValueError("a playout landing power other than 0 needs evaluator='rollout'")
     prior = _lib.rollout_prior_powers(rollout_prior)
     if prior != (0, 0, 0) and (_evaluator_of(driver, driver_kw) != "rollout"):
         raise ValueError("a rollout prior other than 'uniform' needs evaluator='rollout'")
@@ -363,11 +369,14 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
         sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
-                             playout_incumbents=bool(playout_incumbents), playout_policy=policy, rollout_prior=prior, **driver_kw)
+                             playout_incumbents=bool(playout_incumbents), playout_policy=policy, rollout_prior=prior, playout_landing=landing,
+                             **driver_kw)
     elif sp.playout_incumbents != bool(playout_incumbents):
         raise RuntimeError("the driver was built with playout_incumbents=%r" % sp.playout_incumbents)
     elif sp.playout_policy != policy:
         raise RuntimeError("the driver was built with playout_policy=%r" % (sp.playout_policy,))
+    elif sp.playout_landing != landing:
+        raise RuntimeError("the driver was built with playout_landing=%r" % (sp.playout_landing,))
     elif sp.rollout_prior != prior:
         raise RuntimeError("the driver was built with rollout_prior=%r" % (sp.rollout_prior,))
     elif sp.move_rule != rule:
@@ -381,15 +390,17 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
 
 
 def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=None, bin_w=None, initial_board=None, remaining=None,
-                  playout_policy="uniform"):
+                  playout_policy="uniform", playout_landing=0):
     """Scores of random packings -> float64 [n, playouts]: `playouts` random playouts of every instance from the empty bin, or
     from (initial_board, remaining) as pack() takes them
     (rp_rollout_states; instance i plays as episode i, playout j draws from (seed, i, j)).  The random baseline a search or a trained
     network is compared with, and -- flattened -- a first R2 buffer for pack(..., evaluator="rollout", rewards_list=...).
     item_wh / seeds / bin_h / bin_w: the instances, as pack() takes them.  playout_policy: uniform over the legal moves by default, or
-    weighted by the item as pack() takes it -- a buffer for a search under a policy wants the scores of that policy."""
+    weighted by the item as pack() takes it -- a buffer for a search under a policy wants the scores of that policy.  playout_landing: the
+    playouts' landing power, likewise."""
     _check_instances(item_wh, seeds, initial_board, remaining)
     policy = _lib.playout_policy_powers(playout_policy)
+    landing = _lib.playout_landing_power(playout_landing)
     W, H, N = game.bin_width, game.bin_height, game.num_items
     rows0 = rem0 = None
     if seeds is None:  # checked before an engine is built
@@ -398,6 +409,8 @@ def random_scores(game, item_wh=None, seeds=None, playouts=16, seed=0, bin_h=Non
     try:
         if policy != (0, 0):
             eng.set_playout_policy(*policy)
+        if landing != 0:
+            eng.set_playout_landing(landing)
         if seeds is not None:
             item_wh = eng.generate_items(seeds, bin_w=bin_w, bin_h=bin_h)
             area = np.full(len(item_wh), int(bin_w or W) * int(bin_h or H), np.int32)
