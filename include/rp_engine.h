@@ -62,8 +62,31 @@ typedef enum rp_move_rule {
     RP_MOVE_EXTERNAL = 0,   /* host supplies actions through rp_advance_roots */
     RP_MOVE_ARGMAX_FIRST = 1, /* lowest-index argmax of the root visit counts */
     RP_MOVE_SAMPLE = 2,     /* a ~ counts with a counter-based RNG keyed by (seed, episode id, move) */
-    RP_MOVE_ARGMAX_DRAW = 3 /* argmax of the root visit counts, ties drawn uniformly (MCTS_bpp.py:45-46): entry umulhi(x, m) of the
+    RP_MOVE_ARGMAX_DRAW = 3, /* argmax of the root visit counts, ties drawn uniformly (MCTS_bpp.py:45-46): entry umulhi(x, m) of the
                              * m most-visited actions in ascending order, x from the RP_MOVE_SAMPLE stream of (episode id, move) */
+    RP_MOVE_INCUMBENT = 4   /* the move of CoachBPP.py:86-99 follows the episode's incumbent (rp_set_incumbent): keep the best line and play
+                             * along it, the usual step of single-player Monte-Carlo search.  When a slot's search budget is spent, m moves
+                             * have been played and I is its running incumbent -- what rp_incumbents would return at that moment, every
+                             * offer of the move's simulations made (tree terminals, MCTS_bpp.py:78-83, and under rp_set_incumbent_playouts
+                             * the playouts of MCTS_bpp.py:87).  I is FOLLOWABLE iff (1) the slot has one (moves >= 0), (2) score > 0 -- a
+                             * score of 0 is a packing that dropped an item (getRankedReward, BinPackingGame.py:188-212); the first terminal
+                             * of an episode enters the record even so, and such a line leads nowhere --, (3) I.moves > m: it has a next
+                             * action, (4) I.action[q] == the move played at q for every q < m: its line passes through the root.  If I is
+                             * followable the move is I.action[m], played exactly as rp_advance_roots plays an external action (getNextState,
+                             * BinPackingGame.py:58-76): a legal move the search never tried gets its visited entry, a child that does not
+                             * exist yet is materialised and, if terminal, offered.  Otherwise the move is RP_MOVE_ARGMAX_FIRST's.  Examples
+                             * (the root's visit counts, or the one-hot on the played action), trace, the played prefix of the incumbent
+                             * record and the restart are those of every rule.  Condition 4 makes the rule well defined after a mid-episode
+                             * rp_set_move_rule and under every order of calls; with the rule in force since the episode began it always
+                             * holds for an incumbent with score > 0, because a replacement is found from the current root.  Consequences:
+                             *  - under the rule from the start of an episode, a finished episode with best score > 0 has best action ==
+                             *    the played actions, best score == played score, best outcome == played outcome, best board == final board;
+                             *  - the rule reads nothing but the incumbent record and the root, so the played line stays a function of the
+                             *    search alone: not of the slot, rp_set_step_cap, rp_set_compact_rows or graph replay;
+                             *  - counter [14] of rp_counters counts the moves that followed the incumbent; 0 under rules 0 to 3.
+                             * Needs the incumbents: rp_set_move_rule(ctx, 4, ..) while they are off and rp_set_incumbent(ctx, 0) while the
+                             * rule is in force are RP_ERR_STATE, rp_create with move_rule == 4 is RP_ERR_ARG (a new context keeps no
+                             * incumbents yet: set the rule afterwards); a refused call changes nothing. */
 } rp_move_rule;
 
 /* game phases reported by rp_game_status; RP_PHASE_FAILED: a device error stopped this slot's episode (see rp_check) */
@@ -185,7 +208,8 @@ int rp_set_step_cap(rp_ctx *ctx, int32_t max_sims_per_step);
  * convolution work.  Rows past the count hold stale data.  Scheduling only: results do not depend on it. */
 int rp_set_compact_rows(rp_ctx *ctx, int32_t enable);
 /* Switches the move rule; onehot_examples != 0 records pi as a one-hot on the played action, the greedy branch of
- * MCTS.getActionProb (greedy_a == 0, MCTS_bpp.py:43-49) that CoachBPP uses after iterStepThreshold (CoachBPP.py:132). */
+ * MCTS.getActionProb (greedy_a == 0, MCTS_bpp.py:43-49) that CoachBPP uses after iterStepThreshold (CoachBPP.py:132).  RP_ERR_ARG outside
+ * rp_move_rule; RP_ERR_STATE for RP_MOVE_INCUMBENT while incumbents are off.  A refused call changes nothing. */
 int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples);
 /* Placement trace: with enable != 0 every move played on the device -- by any rp_move_rule, rp_advance_roots included -- is recorded
  * as (action, rows): action = item * W + column as BinPackingGame.getNextState takes it (BinPackingGame.py:58-76, item and column
@@ -218,7 +242,7 @@ int rp_set_trace(rp_ctx *ctx, int32_t enable);
  * on, rp_search_step launches one more small kernel, and a slot's launch ends with the simulation that brought a terminal into its tree
  * (it goes on in the next one, as under rp_set_step_cap: scheduling only).  Kernel arguments are baked into captured graphs: re-capture
  * after switching.  Records of episodes that finished while incumbents were off carry none: drain the ring before switching.
- * rp_set_roots is refused while they are on. */
+ * rp_set_roots is refused while they are on.  rp_set_incumbent(ctx, 0) is RP_ERR_STATE while RP_MOVE_INCUMBENT is in force. */
 int rp_set_incumbent(rp_ctx *ctx, int32_t enable);
 /* Playout incumbents: with enable != 0 every playout that rp_rollout_eval runs for a waiting leaf (MCTS_bpp.py:87) is a candidate for
  * the slot's incumbent too -- plain single-player MCTS practice: keep the best rollout.  Off by default; off, records, device bytes and
@@ -448,7 +472,8 @@ int rp_game_status(rp_ctx *ctx, int32_t first, int32_t count, int32_t *phase_out
 /* Return value of each slot's latest simulation (MCTS.search returns v, MCTS_bpp.py:83,104,139) and its kind. */
 int rp_last_values(rp_ctx *ctx, int32_t first, int32_t count, double *v_out, int32_t *kind_out);
 /* Plays `action[i]` in slot first+i (CoachBPP.py:88-91): the child becomes the root, the tree is
- * kept; ended_out[i] = 0 / +-1 as getGameEnded, score_out[i] = r.  Only with RP_MOVE_EXTERNAL. */
+ * kept; ended_out[i] = 0 / +-1 as getGameEnded, score_out[i] = r.  Only with RP_MOVE_EXTERNAL; RP_ERR_STATE under RP_MOVE_INCUMBENT,
+ * whose line an outside move would leave. */
 int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const int32_t *action, int32_t *ended_out,
                      double *score_out);
 /* Finished episodes since the last call (auto move rules): up to max_n records, oldest first. */
@@ -494,7 +519,8 @@ int rp_incumbent_sources(rp_ctx *ctx, int32_t first, int32_t count, int32_t *tre
  * [2] terminal returns, [3] path edges walked, [4] sum of n_valid at selected nodes, [5] sum of n_valid at
  * expanded leaves, [6] transposition links, [7] nodes created, [8] moves played, [9] episodes finished,
  * [10] hash probes (64-slot windows), [11] key bytes compared, [12] sum of visited edges at selected nodes,
- * [13] visited-edge entries created, [14..15] reserved. */
+ * [13] visited-edge entries created, [14] moves that followed the incumbent (RP_MOVE_INCUMBENT; 0 under every other rule),
+ * [15] reserved. */
 int rp_counters(rp_ctx *ctx, int64_t *out16, int32_t reset);
 
 /* ---- replay buffer (CoachBPP.executeEpisode's trainExamples, CoachBPP.py:80,99) -------- */

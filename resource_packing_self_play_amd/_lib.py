@@ -15,12 +15,13 @@ LIB_PATH = os.environ.get("RP_ENGINE_LIB") or os.path.join(HERE, "csrc", "librp_
 ABI_VERSION = 10
 
 MOVE_EXTERNAL, MOVE_ARGMAX_FIRST, MOVE_SAMPLE, MOVE_ARGMAX_DRAW = 0, 1, 2, 3
+MOVE_INCUMBENT = 4  # RP_MOVE_INCUMBENT: the move follows the episode's incumbent where it is followable, else ARGMAX_FIRST; needs set_incumbent(True)
 PHASE_IDLE, PHASE_RUNNING, PHASE_WAIT_EVAL, PHASE_MOVE_READY, PHASE_EPISODE_DONE, PHASE_FAILED = range(6)
 KIND_WEAK, KIND_F32, KIND_F64 = 0, 1, 2
 ERR_ARG, ERR_DEVICE, ERR_CAPACITY, ERR_ASSERT, ERR_STATE = -1, -2, -3, -4, -5
 COUNTER_NAMES = ("simulations", "expansions", "terminal_returns", "path_edges", "sum_valid_select", "sum_valid_leaf",
                  "transposition_links", "nodes", "moves", "episodes", "hash_probes", "key_bytes", "sum_visited_select", "visited_new",
-                 "reserved0", "reserved1")
+                 "followed_moves", "reserved1")
 
 
 class RpConfig(C.Structure):
@@ -233,6 +234,9 @@ class Engine:
 
     def __init__(self, W, H, N, games, sims, cpuct=1.0, alpha=0.75, move_rule=MOVE_EXTERNAL, seed=0, tie_salt=0,
                  node_cap=0, edge_cap=0, device=0, stream=0, auto_restart=0, max_examples=0, vis_cap=0, reclaim=0, max_sparse=0):
+        if int(move_rule) == MOVE_INCUMBENT:  # rp_create refuses it too: a new context keeps no incumbents yet
+            raise ValueError("MOVE_INCUMBENT follows the incumbents, which a new engine does not keep yet: create it with another rule "
+                             "(MOVE_ARGMAX_FIRST is the rule's own fallback), then set_incumbent(True) and set_move_rule(MOVE_INCUMBENT)")
         self.L = load()
         self.W, self.H, self.N, self.A, self.G, self.sims = int(W), int(H), int(N), int(W) * int(N), int(games), int(sims)
         self.move_rule = int(move_rule)
@@ -369,6 +373,8 @@ class Engine:
         self._ck(self.L.rp_set_stream(self.h, C.c_void_p(stream_handle or None)))
 
     def set_move_rule(self, move_rule, onehot_examples=False):
+        """rp_set_move_rule.  MOVE_INCUMBENT needs set_incumbent(True) first (EngineError ERR_STATE otherwise), and set_incumbent(False) is
+        refused while it is in force."""
         self._ck(self.L.rp_set_move_rule(self.h, int(move_rule), 1 if onehot_examples else 0))
         self.move_rule = int(move_rule)
 

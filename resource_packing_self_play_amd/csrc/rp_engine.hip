@@ -49,7 +49,7 @@ typedef unsigned char u8;
 #define MAX_MASK_WORDS 256 /* A <= 8192 */
 
 enum { CNT_SIMS = 0, CNT_EXPAND, CNT_TERMINAL, CNT_PATH, CNT_NVALID_SEL, CNT_NVALID_LEAF, CNT_TRANSPOSE, CNT_NODES,
-       CNT_MOVES, CNT_EPISODES, CNT_PROBES, CNT_KEYBYTES, CNT_VIS_SEL, CNT_VIS_NEW, CNT_RES0, CNT_RES1, CNT_N };
+       CNT_MOVES, CNT_EPISODES, CNT_PROBES, CNT_KEYBYTES, CNT_VIS_SEL, CNT_VIS_NEW, CNT_FOLLOWED, CNT_RES1, CNT_N };
 enum { ERR_NODE_CAP = 1, ERR_EDGE_CAP = 2, ERR_TABLE_FULL = 3, ERR_BAD_ACTION = 4, ERR_PATH = 5, ERR_FINISHED_CAP = 6, ERR_EXAMPLES_CAP = 7, ERR_VIS_CAP = 8, ERR_BAD_EXAMPLE = 9 };
 
 struct NodeHdr {    // 32 bytes = two dwordx4 loads per visited node
@@ -1149,7 +1149,13 @@ __device__ void finish_episode_impl(const DP &p, Tree<row_t, BIG> &t, int g, con
 // CoachBPP.executeEpisode's move (CoachBPP.py:86-99) for one slot whose search budget is spent.
 // action < 0: pick by p.move_rule.  Leaves phase RUNNING or FAILED, or reports the episode's end (the caller writes its record:
 // finish_episode_impl).  DRAW = false (k_advance, which always passes an
-// action) leaves the RP_MOVE_ARGMAX_DRAW branch out of the kernel.
+// action) leaves the RP_MOVE_ARGMAX_DRAW branch and the RP_MOVE_INCUMBENT rule out of the kernel.
+// RP_MOVE_INCUMBENT: the slot's running incumbent is FOLLOWABLE iff it exists, scores above 0, has a next action (moves > the moves
+// played) and its line passes through the root (action[q] == played[q] for every q below the moves played: lane l compares q = l and
+// l + 64, one ballot decides).  Then action[moves played] is played as an external action is -- the branch below that appends the
+// visited entry of a move the search never tried and materialises a missing child -- else the move of RP_MOVE_ARGMAX_FIRST.  Every
+// offer of the move's simulations is in the record by now: k_search leaves a slot MOVE_READY only in a launch after the one whose
+// k_incumbent made the last tree offer, and the playout offers of k_rollout precede the commit that counts their simulation.
 template <typename row_t, bool BIG, bool DRAW = true>
 __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u32 &root, int action) {
     const EpisodeEnd none = {0, 0, 0, NONE32, 0ull};
@@ -1158,6 +1164,17 @@ __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u3
     const int lane = lane_id();
     u32 chosen = NONE32;  // visited entry of the move that is played
     int free_action = -1;  // legal move played from a root the search never expanded (no statistics to keep)
+    bool followed = false;
+    if (DRAW && action < 0 && p.move_rule == RP_MOVE_INCUMBENT && p.inc) {
+        const IncRec rec(p.inc + (size_t)g * p.inc_stride, p.H, p.N);
+        const int inc_moves = uni(rec.meta()[1]), mv = uni(p.moves[g]);
+        if (inc_moves > mv && mv < p.N) {  // it exists (moves >= 0) and has a next action
+            const u16 *line = rec.action(), *played = rec.played();
+            bool off_line = !(*rec.score() > 0.0);  // a packing that dropped an item (score 0) leads nowhere
+            for (int q = lane; q < mv; q += 64) off_line |= line[q] != played[q];
+            if (!__ballot(off_line)) { action = uni((int)line[mv]); followed = true; }
+        }
+    }
     if (action >= 0) {
         u32 ksel = NONE32;
         for (u32 kb = 0; kb < hd.n_valid; kb += 64) {
@@ -1171,7 +1188,7 @@ __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u3
         } else if (ksel != NONE32) {
             free_action = action;
         }
-    } else if (p.move_rule == RP_MOVE_ARGMAX_FIRST) {  // most visited, lowest action among equals
+    } else if (p.move_rule == RP_MOVE_ARGMAX_FIRST || (DRAW && p.move_rule == RP_MOVE_INCUMBENT)) {  // most visited, lowest action among equals
         u32 best_n = 0, best_k = NONE32, best_e = NONE32;
         for (u32 j = lane; j < hd.vis_n; j += 64) {
             u32 e = hd.vis_off + j, n = t.vis[e].n & NSA_MASK, k = t.vis[e].idx;
@@ -1303,6 +1320,7 @@ __device__ EpisodeEnd play_move_impl(const DP &p, Tree<row_t, BIG> &t, int g, u3
     }
     root = child;
     t.count(CNT_MOVES);
+    if (DRAW && followed) t.count(CNT_FOLLOWED);
     NodeHdr ch = t.hdr[child];
     int moves = p.moves[g] + 1;
     if (lane == 0) { p.root[g] = root; p.moves[g] = moves; p.sims_done[g] = 0; }
@@ -1524,11 +1542,14 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_incumbent(DP p) {
     if (lane == 0) p.inc_new[g].node = NONE32;
 }
 
-// CoachBPP.executeEpisode's move for every slot whose search budget is spent (RP_MOVE_ARGMAX_FIRST / RP_MOVE_SAMPLE), and the
-// next instance of the pool for a slot whose episode ended.  Launched right before k_search; a separate kernel so that the
+// CoachBPP.executeEpisode's move for every slot whose search budget is spent (every rp_move_rule but RP_MOVE_EXTERNAL: the rules that
+// read the root's visit counts and RP_MOVE_INCUMBENT, which reads the slot's incumbent record first), and the next instance of the pool for a slot whose episode ended.  Launched right before k_search; a separate kernel so that the
 // simulation loop does not carry this code's registers.
+// Four waves per SIMD asked for: with RP_MOVE_INCUMBENT the external-action branch of play_move_impl is live here too (a constant
+// action = -1 used to fold it away, and s_vmask with it) and the kernel would take one register more than the 128 that four waves
+// leave (make resource-usage); under the bound it keeps 128, without scratch.
 template <typename row_t>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) k_moves(DP p) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, 4) k_moves(DP p) {
     const int g = blockIdx.x * WAVES_PER_BLOCK + wave_in_block();
     if (g >= p.G) return;
     if (p.phase[g] != RP_PHASE_MOVE_READY) return;
@@ -5160,6 +5181,8 @@ extern "C" int rp_create(const rp_config *cfg, rp_ctx **out) {
     if (cfg->games < 1 || cfg->sims < 0) return fail(nullptr, RP_ERR_ARG, "games >= 1 and sims >= 0 required");
     if (!(cfg->cpuct > 0.0)) return fail(nullptr, RP_ERR_ARG, "cpuct must be positive (got %g): the best unvisited move of a node is kept as the one with the largest prior, which is the PUCT winner among the unvisited moves only for cpuct > 0", cfg->cpuct);
     if ((int64_t)cfg->sims * (cfg->N + 1) >= (int64_t)NSA_MASK) return fail(nullptr, RP_ERR_ARG, "sims too large");
+    if (cfg->move_rule == RP_MOVE_INCUMBENT)
+        return fail(nullptr, RP_ERR_ARG, "move_rule RP_MOVE_INCUMBENT follows the incumbents, which a new context does not keep yet: rp_set_incumbent(ctx, 1), then rp_set_move_rule");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device)
         return fail(nullptr, RP_ERR_DEVICE, "no HIP device %d (found %d): the engine has no CPU fallback", cfg->device, ndev);
@@ -5588,7 +5611,9 @@ extern "C" int rp_debug_set_nn_rows(rp_ctx *ctx, const int *rows_dev) {
 }
 
 extern "C" int rp_set_move_rule(rp_ctx *ctx, int32_t move_rule, int32_t onehot_examples) {
-    if (!ctx || move_rule < RP_MOVE_EXTERNAL || move_rule > RP_MOVE_ARGMAX_DRAW) return fail(ctx, RP_ERR_ARG, "rp_set_move_rule: bad argument");
+    if (!ctx || move_rule < RP_MOVE_EXTERNAL || move_rule > RP_MOVE_INCUMBENT) return fail(ctx, RP_ERR_ARG, "rp_set_move_rule: bad argument");
+    if (move_rule == RP_MOVE_INCUMBENT && !ctx->d.inc)
+        return fail(ctx, RP_ERR_STATE, "rp_set_move_rule: RP_MOVE_INCUMBENT follows the incumbents, which are off (rp_set_incumbent(ctx, 1) first)");
     ctx->d.move_rule = move_rule;
     ctx->d.onehot_examples = onehot_examples ? 1 : 0;
     ctx->cfg.move_rule = move_rule;
@@ -5651,6 +5676,8 @@ static void unpack_incumbents(const DP &d, u8 *buf, size_t n, const BestOut &out
 extern "C" int rp_set_incumbent(rp_ctx *ctx, int32_t enable) {
     if (!ctx) return fail(ctx, RP_ERR_ARG, "rp_set_incumbent: bad argument");
     DP &d = ctx->d;
+    if (!enable && d.move_rule == RP_MOVE_INCUMBENT)
+        return fail(ctx, RP_ERR_STATE, "rp_set_incumbent: RP_MOVE_INCUMBENT is in force and follows the incumbents; switch the move rule first (rp_set_move_rule)");
     {   // not while episodes are being played: the terminals their trees already hold would be missing
         std::vector<int> ph((size_t)d.G);
         HIPCHK(ctx, hipMemcpyAsync(ph.data(), d.phase, (size_t)d.G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -6128,6 +6155,8 @@ extern "C" int rp_game_status(rp_ctx *ctx, int32_t first, int32_t count, int32_t
 
 extern "C" int rp_advance_roots(rp_ctx *ctx, int32_t first, int32_t count, const int32_t *action, int32_t *ended_out, double *score_out) {
     if (!ctx || first < 0 || count < 0 || first + count > ctx->d.G || !action) return fail(ctx, RP_ERR_ARG, "rp_advance_roots: bad argument");
+    if (ctx->d.move_rule == RP_MOVE_INCUMBENT)  // an outside move would take the line away from the rule that follows the record
+        return fail(ctx, RP_ERR_STATE, "rp_advance_roots: RP_MOVE_INCUMBENT plays its own moves; external actions need RP_MOVE_EXTERNAL");
     if (count == 0) return RP_OK;
     const DP &d = ctx->d;
     Scratch s(ctx);

@@ -35,8 +35,9 @@ class _Group:
         self.index = index
         self.G = games
         self.stream = torch.cuda.Stream(owner.device)
+        follow = owner.move_rule == _lib.MOVE_INCUMBENT  # a new engine keeps no incumbents yet: the rule is set behind set_incumbent below
         self.eng = _lib.Engine(owner.W, owner.H, owner.N, games, int(owner.args.numMCTSSims), cpuct=float(owner.args.cpuct),
-                               alpha=float(owner.args.alpha), move_rule=owner.move_rule, seed=seed,
+                               alpha=float(owner.args.alpha), move_rule=_lib.MOVE_ARGMAX_FIRST if follow else owner.move_rule, seed=seed,
                                tie_salt=(seed ^ 0x5DEECE66D) if owner.tie_salt is None else int(owner.tie_salt),
                                node_cap=owner.node_cap, edge_cap=owner.edge_cap, device=owner.device.index or 0,
                                stream=self.stream.cuda_stream, auto_restart=1, max_examples=owner.max_examples_per_group,
@@ -47,6 +48,8 @@ class _Group:
             self.eng.set_trace(True)
         if owner.record_best:
             self.eng.set_incumbent(True)
+        if follow:
+            self.eng.set_move_rule(_lib.MOVE_INCUMBENT)
         if owner.playout_incumbents:
             self.eng.set_incumbent_playouts(True)
         if owner.playout_policy != (0, 0):
@@ -157,6 +160,8 @@ class BatchedSelfPlay:
         record_best: the engines keep every episode's incumbent (rp_set_incumbent) -- the best complete packing its search tree saw,
         which the played one cannot beat; the finished episodes' incumbents are collected for pop_best_packings().  Tree terminals only,
         unless playout_incumbents is on.
+        move_rule: a rule of _lib.  _lib.MOVE_INCUMBENT (the move follows the episode's incumbent where that is followable, else the first
+        argmax of the visit counts: rp_engine.h) needs record_best=True, else ValueError.
         playout_incumbents: with record_best and evaluator="rollout", every playout is a candidate too (rp_set_incumbent_playouts): each
         evaluated leaf offers its best playout, and an incumbent's `tree_moves` / `playout` say where it came from.  ValueError
         without record_best or with another evaluator.
@@ -199,6 +204,8 @@ class BatchedSelfPlay:
         self.wide_logits = bool(wide_logits)
         self.record_packings = bool(record_packings)  # set before the groups are built: their waves are captured with it
         self.record_best = bool(record_best)  # likewise
+        if move_rule == _lib.MOVE_INCUMBENT and not self.record_best:
+            raise ValueError("move_rule=MOVE_INCUMBENT follows the incumbents: it needs record_best=True")
         self.playout_incumbents = bool(playout_incumbents)  # likewise
         if self.playout_incumbents and not (self.record_best and rollout):
             raise ValueError("playout_incumbents needs record_best=True and evaluator='rollout'")
@@ -296,6 +303,9 @@ class BatchedSelfPlay:
         self.steps += 1
 
     def set_move_rule(self, move_rule, onehot_examples=False):
+        """Switches the move rule of every group; re-captures the waves.  _lib.MOVE_INCUMBENT needs record_best on (ValueError)."""
+        if move_rule == _lib.MOVE_INCUMBENT and not self.record_best:
+            raise ValueError("move_rule=MOVE_INCUMBENT follows the incumbents: set_record_best(True) first")
         for g in self.groups:
             g.eng.set_move_rule(move_rule, onehot_examples)
         self.move_rule = move_rule
@@ -312,7 +322,9 @@ class BatchedSelfPlay:
     def set_record_best(self, on=True, playout_incumbents=False):
         """Switches the incumbents of every group between pools (refused while episodes are being played); re-captures the waves.
         playout_incumbents: the playouts of evaluator="rollout" are candidates too (ValueError with `on` false or another evaluator);
-        switching the incumbents off switches it off."""
+        switching the incumbents off switches it off.  Off under move_rule MOVE_INCUMBENT: ValueError (switch the rule first)."""
+        if not on and self.move_rule == _lib.MOVE_INCUMBENT:
+            raise ValueError("move_rule MOVE_INCUMBENT is in force and follows the incumbents: set_move_rule to another rule first")
         if playout_incumbents and not (on and self.evaluator == "rollout"):
             raise ValueError("playout_incumbents needs record_best on and evaluator='rollout'")
         for g in self.groups:

@@ -335,7 +335,11 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     saw (rp_set_incumbent; the first found among equals), with `prefix`, `updates` and `played` -- the played Packing -- set.  Its own
     final state is in every episode's tree, so best.score >= best.played.score always.  Tree terminals only, unless playout_incumbents
     is on.  A driver passed in must have been built with record_best=True.
-    playout_incumbents (with best and evaluator="rollout"): every random playout the search runs is a candidate too
+    move_rule=_lib.MOVE_INCUMBENT: every move follows the episode's incumbent where that is followable (it scores above 0 and its line
+    passes through the current state), else the first argmax of the visit counts (rp_engine.h: RP_MOVE_INCUMBENT).  The played packing
+    then IS the incumbent wherever the incumbent scores above 0, so it works with and without best=True: without it the played packings
+    come back, and the driver is still built with record_best=True.  A driver passed in without record_best is a RuntimeError.
+    playout_incumbents (with best or move_rule=MOVE_INCUMBENT, and evaluator="rollout"): every random playout the search runs is a candidate too
     (rp_set_incumbent_playouts) -- in a network-free search they are nearly all the finished packings it ever computes; the incumbents
     then carry `tree_moves` and `playout`.  A driver passed in must have been built with the same setting.
     playout_policy (with evaluator="rollout"): how the playouts choose among the legal moves (rp_set_playout_policy) -- "uniform" (the
@@ -363,12 +367,15 @@ def pack(game, nnet, args, item_wh=None, seeds=None, bin_h=None, move_rule=None,
     n = len(item_wh) if seeds is None else len(seeds)
     rule = greedy_rule(args) if move_rule is None else int(move_rule)
     sp = driver
-    if playout_incumbents and not best:
-        raise ValueError("playout_incumbents is a property of the incumbents: it needs best=True")
+    follow = rule == _lib.MOVE_INCUMBENT  # the rule plays along the incumbents: the driver keeps them whether they are returned or not
+    if playout_incumbents and not (best or follow):
+        raise ValueError("playout_incumbents is a property of the incumbents: it needs best=True or move_rule=MOVE_INCUMBENT")
+    if follow and sp is not None and not sp.record_best:
+        raise RuntimeError("the driver was built without record_best")
     if sp is None:
         games = int(games or min(max(n, 1), 4096))
         driver_kw.setdefault("groups", max(1, min(2, games)))
-        sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best),
+        sp = BatchedSelfPlay(game, nnet, args, games=games, move_rule=rule, seed=seed, max_examples=0, record_packings=True, record_best=bool(best) or follow,
                              playout_incumbents=bool(playout_incumbents), playout_policy=policy, rollout_prior=prior, playout_landing=landing,
                              **driver_kw)
     elif sp.playout_incumbents != bool(playout_incumbents):
